@@ -19,7 +19,25 @@ all inside libdips_hip.so.  (DIPS_BENCH_SHARD=torch runs the older
 Python-level protocol of dips_amd.shard over torch.distributed instead.)
 Frames are generated into HBM by the shared integer generator before timing.
 
-After the timed steps, at every N (the driver's 8-GPU run included):
+A plain run does only what the headline figure needs: it generates the
+frames, warms up, times --steps steps, writes the outputs of the last timed
+step when --dump-outputs DIR is given, and prints the line ("value" and
+"ms_per_step" from the timed steps, "roofline" from the series kernel's
+hipEvent times inside them).  Every other measurement and check below takes
+runs of its own and is made only with --full; without it their keys are null.
+
+--dump-outputs DIR (rank 0): what a caller of the timed path receives from the
+last timed step, the gathered series of all N*F frames, as float64 .npy files
+(the frames are generated from a fixed seed, so two builds run with the same
+arguments can be compared file by file):
+  * series.npy [N*F, 4]: sad, sj, count and the intensity sum si_fixed * 2^-32
+    (dips_series_si; sad, sj and count are exact in float64);
+  * si_fixed_hi32.npy, si_fixed_lo32.npy [N*F]: the upper and lower 32 bits of
+    si_fixed, so the 64-bit fixed-point sum can be compared exactly.
+
+With --full, after the timed steps, at every N:
+  * "roofline.read_ceiling", "power": measured read-only ceilings over the same
+    frames and the socket power over each leg;
   * "check": every rank re-derives its first series entries against the halo
     / reference it received, rank 0 the gathered rows at every shard boundary
     and 8 random frames (dips_amd.shard.verify_sharded_series); a mismatch
@@ -30,9 +48,10 @@ After the timed steps, at every N (the driver's 8-GPU run included):
     resident buffer, each with frames/s, roofline fraction, RCCL times and
     its own check;
   * at N = 1 also "per_frame_call": the reference's own pattern, one 4K RGBA8
-    frame per dips_frame_callback from pageable host memory.
+    frame per dips_frame_callback from pageable host memory; "cpu_baseline",
+    "tau0", "pcie_inclusive" and "map_variant".
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]; for N > 1 under
 torch.distributed.run (one process per GPU, RANK/LOCAL_RANK/WORLD_SIZE).
 Prints ONE JSON line on rank 0.
 """
@@ -66,6 +85,13 @@ def parse():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--mode", choices=["per-frame", "overall"], default="per-frame")
     ap.add_argument("--tau", type=float, default=8.0 / 255.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check (power, read ceilings, "
+                         "self-check, cpu_baseline, tau0, pcie_inclusive, map_variant, per_frame_call, the "
+                         "configs[3] / configs[4] legs); the --no-* options below switch single ones off again")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the gathered series of the last timed step to DIR as float64 .npy files "
+                         "(series.npy, si_fixed_hi32.npy, si_fixed_lo32.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true",
                     help="skip the pcie_inclusive sample (profiling runs: its chunk launches of the series "
@@ -117,6 +143,21 @@ def _v2_kernel_name(per_frame: bool, tau: float, with_map: bool = False) -> str:
 
 def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+def _dump_outputs(dirname: str, series_u64: np.ndarray) -> None:
+    """--dump-outputs: the gathered series (uint64 [n, 4]) as float64 files.
+    sad, sj and count stay below 2^53 at any frame size the library takes, so
+    series.npy holds them exactly; si_fixed can pass 2^53 at 4K, so series.npy
+    holds the f64 sum a caller reads (si_fixed * 2^-32, dips_series_si) and
+    the two 32-bit halves of si_fixed go beside it, exact."""
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(series_u64, dtype=np.uint64).reshape(-1, 4)
+    ser = a.astype(np.float64)
+    ser[:, 3] = a[:, 3].astype(np.float64) * 2.0 ** -32
+    np.save(os.path.join(dirname, "series.npy"), ser)
+    np.save(os.path.join(dirname, "si_fixed_hi32.npy"), (a[:, 3] >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(dirname, "si_fixed_lo32.npy"), (a[:, 3] & np.uint64(0xFFFFFFFF)).astype(np.float64))
 
 
 def _time_oracle(lib, frames, mode, tau, threads, target_s, max_passes=400):
@@ -919,7 +960,7 @@ def _main(args):
                 shard.per_frame_overlapped(frames, ref, series, compute)
             return gather(series)
 
-    smp = _power_sampler(torch, local) if rank == 0 else None
+    smp = _power_sampler(torch, local) if rank == 0 and args.full else None
     final = None
     for _ in range(args.warmup):
         step()
@@ -950,12 +991,14 @@ def _main(args):
     # throttling the ceiling does not see?): one plain stream over the same
     # resident bytes, and the series kernel's own access shape (tile walk,
     # schedule, 12-B vecs, no compute)
-    reps = max(3, args.steps)
-    read_all, read_power = _power_leg(smp, lambda: [op.read_ceiling_ms(frames) for _ in range(reps)], F * reps,
-                                      f"{reps} back-to-back read_ceiling_kernel launches")
-    walk_all, walk_power = _power_leg(smp, lambda: [op.read_ceiling_walk_ms(frames) for _ in range(reps)],
-                                      F * reps, f"{reps} back-to-back read_walk_kernel launches")
-    read_ms, walk_ms = float(np.median(read_all)), float(np.median(walk_all))
+    read_all = walk_all = None
+    if args.full:
+        reps = max(3, args.steps)
+        read_all, read_power = _power_leg(smp, lambda: [op.read_ceiling_ms(frames) for _ in range(reps)], F * reps,
+                                          f"{reps} back-to-back read_ceiling_kernel launches")
+        walk_all, walk_power = _power_leg(smp, lambda: [op.read_ceiling_walk_ms(frames) for _ in range(reps)],
+                                          F * reps, f"{reps} back-to-back read_walk_kernel launches")
+        read_ms, walk_ms = float(np.median(read_all)), float(np.median(walk_all))
     # series-kernel time per step (one launch per step, two when the halo
     # overlap splits a per-frame batch at N > 1)
     tt = torch.tensor([elapsed, kms / args.steps], dtype=torch.float64, device=dev)
@@ -970,12 +1013,13 @@ def _main(args):
     # received, rank 0 re-derives the gathered rows at every shard boundary
     # and 8 random frames (dips_amd.shard.verify_sharded_series)
     check = None
-    if comm is not None and mode == Mode.PerFrame and world > 1:
+    do_check = args.full and not args.no_check
+    if do_check and comm is not None and mode == Mode.PerFrame and world > 1:
         # what the library compared this rank's first frame with: the halo it
         # received (rank > 0), for the self-check below
         op.shard_reference_device(ref)
         torch.cuda.synchronize()
-    if not args.no_check:
+    if do_check:
         check = shard.verify_sharded_series(op, width=W, height=H, seed=SEED, n_total=world * F,
                                             per_frame=(mode == Mode.PerFrame), local_series=series, ref=ref,
                                             gathered=final, device=dev)
@@ -992,6 +1036,8 @@ def _main(args):
         assert final_np.shape == (world * F, 4)
         if args.dump_series:
             np.save(args.dump_series, final_np)
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, final_np)
         if args.check and world * F * fb > (64 << 30):
             log("--check skipped: the N*F frames would not fit beside the resident batch (small sizes only)")
         elif args.check:
@@ -1004,7 +1050,7 @@ def _main(args):
             assert np.array_equal(final_np, one.cpu().numpy().view(np.uint64)), "gathered series != single-device series"
             log(f"--check: gathered series of {world}x{F} frames equals the single-device series")
             del allf, one
-    if world == 1:
+    if world == 1 and args.full:
         # PCIe-inclusive rate, reported beside (never as) `value` (BASELINE.md:
         # "the H2D end-to-end rate separately"): the first 96 frames copied to
         # pageable host memory and fed back through dips_diff_series_streamed
@@ -1057,7 +1103,7 @@ def _main(args):
     # configs[3] and configs[4] on the same ranks, regenerated into the same
     # resident buffer (collective at N > 1)
     legs = {}
-    if not args.no_legs:
+    if args.full and not args.no_legs:
         op.close()
         op = None
         del series
@@ -1110,6 +1156,7 @@ def _main(args):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed_max / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -1149,7 +1196,7 @@ def _main(args):
                 # (tools/placement.py candidate 0, the median of its probe
                 # launches), beside the headline's kept placement
                 **_plain_allocation(placement, algo_bytes, kernel_ms),
-                "read_ceiling": {
+                "read_ceiling": None if read_all is None else {
                     "achieved": round(F * fb / (read_ms / 1e3) / 1e9, 1),
                     "unit": "GB/s",
                     "frac": round(achieved / (F * fb / (read_ms / 1e3) / 1e9), 4),

@@ -22,7 +22,7 @@ def test_bench_line_keeps_the_contract():
         baseline = json.load(f)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(STEPS), "--warmup", "1",
            "--frames-per-gpu", str(F), "--width", str(W), "--height", str(H), "--cpu-seconds", "0.5",
-           "--no-pcie", "--no-map", "--no-tau0", "--no-legs", "--no-per-frame-call"]
+           "--full", "--no-pcie", "--no-map", "--no-tau0", "--no-legs", "--no-per-frame-call"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -56,3 +56,33 @@ def test_bench_line_keeps_the_contract():
     assert len(ms) == 2 and pl[0]["kept"] == choose(ms[0], ms[1], pl[0]["threshold"])[0]
     assert r["plain_kernel_ms"] == pytest.approx(ms[0], abs=1e-4)
     assert r["plain_frac"] == pytest.approx(F * W * H * 3 / (ms[0] / 1e3) / 1e9 / 8000.0, rel=2e-3)
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline figures only (every other
+    measurement null, --steps launches timed), and --dump-outputs writes the
+    last timed step's series as float64 files: exactly the uint64 series of
+    --dump-series, si_fixed split into exact 32-bit halves."""
+    import numpy as np
+    out, raw = tmp_path / "out", tmp_path / "series.npy"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(STEPS), "--warmup", "1",
+           "--frames-per-gpu", str(F), "--width", str(W), "--height", str(H),
+           "--dump-outputs", str(out), "--dump-series", str(raw)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == STEPS and d["roofline"]["kernel_launches_timed"] == STEPS
+    assert d["value"] == pytest.approx(F / (d["ms_per_step"] / 1e3), rel=2e-3)
+    for key in ("check", "cpu_baseline", "power", "tau0", "pcie_inclusive", "map_variant", "per_frame_call"):
+        assert d[key] is None, key
+    assert d["roofline"]["read_ceiling"] is None and "configs3" not in d and "configs4" not in d
+    want = np.load(raw)
+    assert want.dtype == np.uint64 and want.shape == (F, 4) and want[:, 0].max() > 0
+    assert sorted(os.listdir(out)) == ["series.npy", "si_fixed_hi32.npy", "si_fixed_lo32.npy"]
+    ser, hi, lo = (np.load(out / n) for n in ("series.npy", "si_fixed_hi32.npy", "si_fixed_lo32.npy"))
+    assert ser.dtype == hi.dtype == lo.dtype == np.float64 and ser.shape == (F, 4)
+    assert np.array_equal(ser[:, :3].astype(np.uint64), want[:, :3])
+    assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), want[:, 3])
+    assert np.array_equal(ser[:, 3], want[:, 3].astype(np.float64) * 2.0 ** -32)

@@ -53,7 +53,7 @@ def _run(mode, corrupt, dump=None, frames=F, width=W, height=H, extra=(), env_ex
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--steps", "2", "--warmup", "1", "--frames-per-gpu", str(frames),
            "--width", str(width), "--height", str(height), "--mode", mode,
-           "--leg-steps", "1", "--no-cpu-baseline", "--no-pcie", "--no-map", "--no-per-frame-call",
+           "--leg-steps", "1", "--full", "--no-cpu-baseline", "--no-pcie", "--no-map", "--no-per-frame-call",
            "--dist-timeout", "120", *extra]
     if dump:
         cmd += ["--dump-series", dump]
