@@ -422,6 +422,49 @@ class Series:
         return cls(a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy(), a[:, 3].copy())
 
 
+@dataclass
+class GridSeries:
+    """The difference series per cell of a rows x cols grid
+    (dips_diff_series_grid): every field uint64 [N, rows, cols]."""
+    sad: np.ndarray
+    sj: np.ndarray
+    count: np.ndarray
+    si_fixed: np.ndarray
+
+    @property
+    def si(self) -> np.ndarray:
+        return np.ldexp(self.si_fixed.astype(np.float64), -32)
+
+    def as_array(self) -> np.ndarray:
+        """[N, rows, cols, 4]: sad, sj, count, si_fixed."""
+        return np.stack([self.sad, self.sj, self.count, self.si_fixed], axis=-1)
+
+    @classmethod
+    def from_array(cls, a: np.ndarray) -> "GridSeries":
+        a = np.asarray(a, dtype=np.uint64)
+        return cls(a[..., 0].copy(), a[..., 1].copy(), a[..., 2].copy(), a[..., 3].copy())
+
+
+def _roi_arg(roi):
+    """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
+    if roi is None:
+        return None
+    if len(roi) != 4 or any(int(v) < 0 or int(v) > 0xFFFFFFFF for v in roi):
+        raise ValueError("roi must be (x, y, w, h) of non-negative 32-bit integers")
+    return (ctypes.c_uint32 * 4)(*[int(v) for v in roi])
+
+
+def grid_cell(width: int, height: int, rows: int, cols: int, row: int, col: int,
+              roi=None) -> Tuple[int, int, int, int]:
+    """(x, y, w, h) of cell (row, col) of a rows x cols grid over roi (None:
+    the whole frame), as dips_diff_series_grid cuts it (dips_grid_cell):
+    column c covers [x + c*w//cols, x + (c+1)*w//cols), rows likewise."""
+    rect = (ctypes.c_uint32 * 4)()
+    check(_lib.load().dips_grid_cell(int(width), int(height), _roi_arg(roi), int(rows), int(cols), int(row),
+                                     int(col), rect))
+    return rect[0], rect[1], rect[2], rect[3]
+
+
 def _frame_geometry(frames, fmt: PixelFormat) -> Tuple[int, int, int]:
     shape = tuple(frames.shape)
     c = int(fmt)
@@ -528,6 +571,48 @@ class DiffSeriesOperator:
                 self._dev.ptr, w, h, frames.data_ptr(), n,
                 ref.data_ptr() if ref is not None else None, series_out.data_ptr(),
                 map_out.data_ptr() if map_out is not None else None))
+
+    # -- the series per cell of a spatial grid (dips_diff_series_grid) --------
+    def grid(self, frames: np.ndarray, rows: int, cols: int, roi=None,
+             ref: Optional[np.ndarray] = None) -> GridSeries:
+        """The series of every cell of a rows x cols grid over roi = (x, y,
+        w, h) (None: the whole frame): cell [t, r, c] is the entry this
+        operator gives for the frames and ref cropped to grid_cell(...)."""
+        frames = _as_u8(frames)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        out = np.zeros((n, int(rows), int(cols), 4), dtype=np.uint64)
+        rp = None
+        if ref is not None:
+            ref = _as_u8(ref)
+            if ref.size != h * w * int(self.fmt):
+                raise ValueError("ref must have the shape of one frame")
+            rp = ref.ctypes.data
+        self._host.check(self._host._lib.dips_diff_series_grid(
+            self._host.ptr, w, h, frames.ctypes.data, n, rp, _roi_arg(roi), int(rows), int(cols),
+            out.ctypes.data))
+        return GridSeries.from_array(out)
+
+    def run_grid_device(self, frames, cells_out, rows: int, cols: int, roi=None, ref=None, stream=None) -> None:
+        """Asynchronous: frames / ref uint8 device tensors, cells_out an
+        8-byte device tensor of shape [N, rows, cols, 4]."""
+        n, h, w = _frame_geometry(frames, self.fmt)
+        if tuple(cells_out.shape) != (n, int(rows), int(cols), 4) or cells_out.element_size() != 8:
+            raise ValueError("cells_out must be an 8-byte tensor of shape [N, rows, cols, 4]")
+        for t in (frames, cells_out, ref):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        import torch
+        for t in (frames, ref):
+            if t is not None and t.dtype != torch.uint8:
+                raise ValueError("frames and ref must be uint8 tensors")
+        if ref is not None and ref.numel() != h * w * int(self.fmt):
+            raise ValueError("ref must have the size of one frame")
+        lib = self._dev._lib
+        with _stream_of(self._dev, frames, stream):
+            self._dev.check(lib.dips_diff_series_grid(
+                self._dev.ptr, w, h, frames.data_ptr(), n,
+                ref.data_ptr() if ref is not None else None, _roi_arg(roi), int(rows), int(cols),
+                cells_out.data_ptr()))
 
     # -- frame-range sharding (native: shard_abi.hip) -------------------------
     def run_sharded(self, comm, frames, n_total: int, series_local, series_all=None, ref=None,
@@ -676,6 +761,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "DiffSeriesOperator", "diff_series",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "grid_cell", "DiffSeriesOperator",
+    "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",
 ]

@@ -85,6 +85,72 @@ struct GenericArgs {
     float tau;
 };
 
+// A rows x cols grid over the region of interest {x, y, w, h} of a frame
+// (dips_diff_series_grid).  Column c covers [x + c*w/cols, x + (c+1)*w/cols),
+// rows likewise -- the split dips_shard_range makes of a frame count; host
+// and kernels take every cell rectangle from grid_cell_rect.
+struct GridSpec {
+    uint32_t x, y, w, h;
+    uint32_t rows, cols;
+};
+
+struct GridRect {
+    uint32_t x, y, w, h;
+};
+
+__host__ __device__ inline uint32_t grid_edge(uint32_t x0, uint32_t extent, uint32_t n, uint32_t i) {
+    return x0 + (uint32_t)((uint64_t)i * extent / n);
+}
+
+__host__ __device__ inline GridRect grid_cell_rect(const GridSpec& g, uint32_t row, uint32_t col) {
+    GridRect r;
+    r.x = grid_edge(g.x, g.w, g.cols, col);
+    r.y = grid_edge(g.y, g.h, g.rows, row);
+    r.w = grid_edge(g.x, g.w, g.cols, col + 1) - r.x;
+    r.h = grid_edge(g.y, g.h, g.rows, row + 1) - r.y;
+    return r;
+}
+
+// series_grid_kernel (series_grid.hip): a tile = 64 * U vecs of ONE cell, a
+// vec = 4 horizontally consecutive pixels of one cell row (the last vec of a
+// row may hold fewer), (row, vec-in-row) flattened over the cell.  Every cell
+// owns tiles_per_cell tile ids (the count of the largest cell; the ids past a
+// smaller cell's last tile do nothing and have no records).
+struct GridArgs {
+    const uint8_t* frames;   // n_frames * frame_bytes, contiguous
+    const uint8_t* ref0;     // overall: reference; per-frame: predecessor of frame 0
+    uint64_t* partials;      // [n_cells * tiles_per_cell][n_frames] x 16-byte records
+    uint64_t* zero;          // the cells array, zeroed by the kernel before the reduce's atomics
+    uint32_t zero_n;         // its u64 count (4 * n_frames * n_cells)
+    uint32_t frame_bytes;
+    uint32_t width;          // frame width in pixels (the row pitch)
+    uint32_t n_frames;
+    uint32_t tiles_per_cell;
+    uint32_t n_tiles;        // n_cells * tiles_per_cell
+    uint32_t n_waves;
+    uint32_t part_frames;    // frames per part of the part-major schedule (>= 1)
+    float thr;               // series_threshold()
+    GridSpec g;
+};
+
+// grid_generic_kernel: one thread per pixel of a cell, the reference's own
+// intensity form, u64 atomics into cells[t * out_stride + out_base + cell].
+struct GridGenericArgs {
+    const uint8_t* frames;
+    const uint8_t* ref0;
+    dips_series_entry* cells;
+    uint64_t frame_bytes;
+    uint32_t width;
+    uint32_t n_frames;
+    uint32_t segs_per_cell;  // 256-pixel segments of the largest cell
+    uint32_t out_stride;     // entries per frame of the cells array
+    uint32_t out_base;       // first entry of this launch's cells within a frame's entries
+    uint32_t mode;
+    uint32_t chroma;
+    float tau;
+    GridSpec g;
+};
+
 struct SynthArgs {
     uint8_t* dst;
     uint64_t total_bytes;
@@ -257,6 +323,14 @@ const void* series_gray_lut_kernel_ptr(bool per_frame, bool map);
 hipError_t launch_gray_lut(uint8_t* tab, float tau, int layout, hipStream_t s);
 hipError_t launch_series_gray_lut(const SeriesArgs& a, bool per_frame, bool map, uint32_t blocks, hipStream_t s);
 hipError_t launch_series_generic(const GenericArgs& a, int channels, hipStream_t s);
+// the grid form of the series (series_grid.hip): RGB8 / RGBA8 fast kernel
+// (isi as series_v2), its per-(cell, frame) reduce and the any-format generic
+// kernel
+const void* series_grid_kernel_ptr(int channels, int chroma, bool per_frame, int isi);
+hipError_t launch_series_grid(const GridArgs& a, int channels, int chroma, bool per_frame, int isi, uint32_t blocks,
+                              hipStream_t s);
+hipError_t launch_grid_reduce(const GridArgs& a, int channels, dips_series_entry* cells, hipStream_t s);
+hipError_t launch_grid_generic(const GridGenericArgs& a, int channels, hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 hipError_t launch_read_ceiling(const uint8_t* p, uint64_t bytes, uint32_t* out, hipStream_t s);
 // read-only walk in the RGB8 / RGBA8 series kernel's shape (vec_bytes 12 / 16, U = kUnrollV2Rgb / kUnrollV2)

@@ -20,6 +20,9 @@
 //            with --ranks, dips_alt_run_sharded
 //   dips_raw series IN.raw W H rgb8|rgba8|gray8 [--mode overall|per-frame]
 //            [--tau T] [--chunk N]        -> CSV frame,sad,sj,count,si
+//            [--grid RxC [--roi x,y,w,h]] -> the series per cell of an R x C
+//            grid over the region (default: the whole frame) with
+//            dips_diff_series_grid: CSV t,row,col,sad,sj,count,si_fixed
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -83,7 +86,7 @@ int usage() {
                  "       dips_raw alt IN.rgba W H OUT.rgba [--markers M1,M2,...] [--window N] [--textures N]\n"
                  "                [--ranks N [--transport loopback|rccl]]\n"
                  "       dips_raw series IN.raw W H rgb8|rgba8|gray8 [--mode overall|per-frame] [--tau T]\n"
-                 "                [--chunk N]\n"
+                 "                [--chunk N] [--grid RxC [--roi x,y,w,h]]\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -99,6 +102,29 @@ bool parse_u32(const char* s, uint32_t* v) {
     const unsigned long x = std::strtoul(s, &end, 10);
     if (!s[0] || *end || x == 0 || x > 0xFFFFFFFFul) return false;
     *v = (uint32_t)x;
+    return true;
+}
+
+// "RxC" -> rows, cols (both >= 1)
+bool parse_grid(const std::string& s, uint32_t* rows, uint32_t* cols) {
+    const size_t x = s.find('x');
+    if (x == std::string::npos) return false;
+    return parse_u32(s.substr(0, x).c_str(), rows) && parse_u32(s.substr(x + 1).c_str(), cols);
+}
+
+// "x,y,w,h" -> roi[4] (decimal, zero allowed; the library checks the extent)
+bool parse_roi(const std::string& s, uint32_t* roi) {
+    size_t at = 0;
+    for (int k = 0; k < 4; ++k) {
+        const size_t comma = k < 3 ? s.find(',', at) : s.size();
+        if (comma == std::string::npos || comma == at) return false;
+        const std::string tok = s.substr(at, comma - at);
+        char* end = nullptr;
+        const unsigned long v = std::strtoul(tok.c_str(), &end, 10);
+        if (tok[0] < '0' || tok[0] > '9' || *end || v > 0xFFFFFFFFul) return false;
+        roi[k] = (uint32_t)v;
+        at = comma + 1;
+    }
     return true;
 }
 
@@ -352,7 +378,9 @@ int run_sharded(int argc, char** argv) {
 
 int run_series(int argc, char** argv) {
     if (argc < 6) return usage();
-    uint32_t w = 0, h = 0, chunk = 0;
+    uint32_t w = 0, h = 0, chunk = 0, rows = 0, cols = 0;
+    uint32_t roi[4] = {0, 0, 0, 0};
+    bool has_roi = false;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -370,10 +398,16 @@ int run_series(int argc, char** argv) {
             p.tau = std::strtof(argv[++i], nullptr);
         } else if (a == "--chunk" && has) {
             if (!parse_u32(argv[++i], &chunk)) return usage();
+        } else if (a == "--grid" && has) {
+            if (!parse_grid(argv[++i], &rows, &cols)) return usage();
+        } else if (a == "--roi" && has) {
+            if (!parse_roi(argv[++i], roi)) return usage();
+            has_roi = true;
         } else {
             return usage();
         }
     }
+    if (has_roi && rows == 0) return usage();  // --roi belongs to --grid
     Mapped in;
     if (!in.open(argv[2])) {
         std::fprintf(stderr, "dips_raw: cannot map %s\n", argv[2]);
@@ -388,6 +422,24 @@ int run_series(int argc, char** argv) {
     dips_handle* hd = nullptr;
     int st = dips_create(&p, 0, &hd);
     if (st != DIPS_OK) return lib_error(nullptr, "dips_create", st);
+    if (rows != 0) {
+        std::vector<dips_series_entry> cells((size_t)n * rows * cols);
+        st = dips_diff_series_grid(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, rows, cols, cells.data());
+        if (st != DIPS_OK) {
+            const int rc = lib_error(hd, "dips_diff_series_grid", st);
+            dips_destroy(hd);
+            return rc;
+        }
+        std::printf("t,row,col,sad,sj,count,si_fixed\n");
+        for (size_t i = 0; i < cells.size(); ++i) {
+            const size_t cell = i % ((size_t)rows * cols);
+            std::printf("%zu,%zu,%zu,%llu,%llu,%llu,%llu\n", i / ((size_t)rows * cols), cell / cols, cell % cols,
+                        (unsigned long long)cells[i].sad, (unsigned long long)cells[i].sj,
+                        (unsigned long long)cells[i].count, (unsigned long long)cells[i].si_fixed);
+        }
+        dips_destroy(hd);
+        return 0;
+    }
     std::vector<dips_series_entry> series(n);
     st = dips_diff_series_streamed(hd, w, h, in.p, n, nullptr, series.data(), chunk);
     if (st != DIPS_OK) {

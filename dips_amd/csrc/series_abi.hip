@@ -176,6 +176,21 @@ int series_isi_form(const dips_handle* h) {
     return 1;
 }
 
+// The timing events of a launch (DIPS_FLAG_TIME_KERNEL), back to the handle's
+// free list when the launch function returns without having queued them.
+struct EventReturn {
+    dips_handle* h;
+    hipEvent_t* e0;
+    hipEvent_t* e1;
+    ~EventReturn() {
+        try {
+            if (*e0) h->ev_free.push_back(*e0);
+            if (*e1) h->ev_free.push_back(*e1);
+        } catch (...) {
+        }
+    }
+};
+
 }  // namespace
 
 namespace dips_internal {
@@ -229,18 +244,7 @@ dips_status run_series_device(dips_handle* h, uint32_t width, uint32_t height, c
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // the timing events go back to the free list on every early return; they
     // join ev_pending only once both are recorded
-    struct EventReturn {
-        dips_handle* h;
-        hipEvent_t* e0;
-        hipEvent_t* e1;
-        ~EventReturn() {
-            try {
-                if (*e0) h->ev_free.push_back(*e0);
-                if (*e1) h->ev_free.push_back(*e1);
-            } catch (...) {
-            }
-        }
-    } ev_return{h, &e0, &e1};
+    EventReturn ev_return{h, &e0, &e1};
     if (timing) {
         e0 = take_event(h);
         e1 = take_event(h);
@@ -384,6 +388,170 @@ dips_status run_series_streamed(dips_handle* h, uint32_t width, uint32_t height,
 
 namespace {
 
+// ---------------------------------------------------------------------------
+// The grid form (dips_diff_series_grid; kernels in series_grid.hip)
+// ---------------------------------------------------------------------------
+
+// The grid of a call, validated: nullptr, or why it is refused.
+const char* grid_spec(uint32_t width, uint32_t height, const uint32_t* roi, uint32_t rows, uint32_t cols,
+                      dips::GridSpec* g) {
+    if (width == 0 || height == 0) return "empty frame";
+    g->x = roi ? roi[0] : 0u;
+    g->y = roi ? roi[1] : 0u;
+    g->w = roi ? roi[2] : width;
+    g->h = roi ? roi[3] : height;
+    g->rows = rows;
+    g->cols = cols;
+    if (g->w == 0 || g->h == 0) return "the region of interest has zero extent";
+    if ((uint64_t)g->x + g->w > width || (uint64_t)g->y + g->h > height)
+        return "the region of interest leaves the frame";
+    if (rows == 0 || cols == 0) return "rows and cols must be at least 1";
+    if (rows > g->h || cols > g->w) return "more rows or cols than the region has pixels (a cell would be empty)";
+    return nullptr;
+}
+
+struct GridGeom {
+    bool ok = false;
+    uint32_t tiles_per_cell = 0, part_frames = 0;
+    uint64_t n_tiles = 0, n_waves = 0, blocks = 0;
+};
+
+// Geometry of the fast grid kernel: every cell owns the tile count of the
+// largest cell; a persistent grid of occupancy x CUs waves (fast_geometry's
+// sizing), frames cut into parts as part_geometry cuts them, or for batches
+// it leaves alone into enough parts of >= 16 frames to give every wave slot
+// an item.  Refused (the generic kernel runs): frames of 2^31 bytes or more,
+// 2^28 frames, and grids whose records would outweigh the batch -- cells of a
+// few pixels, where a 16-byte record per (tile, frame) is most of the traffic.
+GridGeom grid_geometry(dips_handle* h, uint32_t width, uint32_t height, uint32_t n_frames, int C, bool pf, int isi,
+                       const dips::GridSpec& g) {
+    GridGeom q;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    if (fb >= (1ull << 31) || n_frames == 0 || n_frames >= (1u << 28)) return q;
+    const void* k = dips::series_grid_kernel_ptr(C, (int)h->p.chroma_filter, pf, isi);
+    if (!k) return q;
+    const uint64_t vpt = 64u * (uint64_t)dips::fast_unroll(C);  // vecs per tile
+    const uint64_t max_w = ((uint64_t)g.w + g.cols - 1) / g.cols, max_h = ((uint64_t)g.h + g.rows - 1) / g.rows;
+    const uint64_t tpc = (((max_w + 3) / 4) * max_h + vpt - 1) / vpt;
+    const uint64_t n_cells = (uint64_t)g.rows * g.cols;
+    const uint64_t n_tiles = n_cells * tpc;
+    if (n_tiles >= (1ull << 31)) return q;
+    const uint64_t rec_bytes = n_tiles * n_frames * 16u;
+    if (rec_bytes > (64ull << 20) && rec_bytes > fb * n_frames) return q;
+    const uint64_t resident = waves_per_simd((uint64_t)occupancy_blocks(h, k), true) * (uint64_t)h->cu_count * 4u;
+    if (resident == 0) return q;
+    FastGeom f;
+    f.n_tiles = n_tiles;
+    part_geometry(f, n_frames, resident);
+    if (f.part_frames != 0) {
+        q.part_frames = f.part_frames;
+        q.n_waves = f.n_waves;
+    } else {
+        const uint64_t want = (resident + n_tiles - 1) / n_tiles;
+        const uint64_t parts = std::max<uint64_t>(1, std::min<uint64_t>(want, n_frames / 16u));
+        q.part_frames = (uint32_t)((n_frames + parts - 1) / parts);
+        const uint64_t items = ((n_frames + q.part_frames - 1) / q.part_frames) * n_tiles;
+        q.n_waves = std::min(items, resident);
+    }
+    q.blocks = (q.n_waves + 3) / 4;
+    q.tiles_per_cell = (uint32_t)tpc;
+    q.n_tiles = n_tiles;
+    q.ok = q.blocks < (1ull << 31);
+    return q;
+}
+
+// Run the grid series on device pointers, asynchronously on `s`.
+dips_status run_grid_device(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames, uint32_t n_frames,
+                            const uint8_t* ref0, const dips::GridSpec& g, dips_series_entry* cells, hipStream_t s) {
+    const int C = (int)h->p.format;
+    const bool pf = h->p.mode == DIPS_MODE_PER_FRAME;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    const uint32_t n_cells = g.rows * g.cols;
+    const int isi = series_isi_form(h);
+    GridGeom q;
+    // GRAY8 has no fast grid kernel; DIPS_FLAG_CROSSCHECK asks for the plain one
+    if (C != 1 && !(h->p.flags & DIPS_FLAG_FORCE_GENERIC) && !h->crosscheck())
+        q = grid_geometry(h, width, height, n_frames, C, pf, isi, g);
+    // the cells start at zero: the fast kernel clears them itself (GridArgs::zero)
+    if (!q.ok) DIPS_HIP(h, hipMemsetAsync(cells, 0, sizeof(dips_series_entry) * (size_t)n_frames * n_cells, s));
+    auto launch_generic = [&](const dips::GridSpec& gs, uint32_t out_base) -> dips_status {
+        const uint64_t max_w = ((uint64_t)gs.w + gs.cols - 1) / gs.cols, max_h = ((uint64_t)gs.h + gs.rows - 1) / gs.rows;
+        const uint64_t spc = (max_w * max_h + 255u) / 256u;
+        if (spc >= (1ull << 32)) return fail(h, DIPS_ERR_INVALID, "diff_series_grid: cell too large for the generic kernel");
+        dips::GridGenericArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.cells = cells;
+        a.frame_bytes = fb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.segs_per_cell = (uint32_t)spc;
+        a.out_stride = n_cells;
+        a.out_base = out_base;
+        a.mode = h->p.mode;
+        a.chroma = C == 1 ? 0u : h->p.chroma_filter;
+        a.tau = h->p.tau;
+        a.g = gs;
+        DIPS_HIP(h, dips::launch_grid_generic(a, C, s));
+        return DIPS_OK;
+    };
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    dips::GridArgs a{};
+    if (q.ok) {
+        DIPS_HIP(h, h->partials.ensure((size_t)q.n_tiles * n_frames * 16u));
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.partials = h->partials.as<uint64_t>();
+        a.zero = reinterpret_cast<uint64_t*>(cells);
+        a.zero_n = 4u * n_frames * n_cells;
+        a.frame_bytes = (uint32_t)fb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.tiles_per_cell = q.tiles_per_cell;
+        a.n_tiles = (uint32_t)q.n_tiles;
+        a.n_waves = (uint32_t)q.n_waves;
+        a.part_frames = q.part_frames;
+        a.thr = dips::series_threshold(C, h->p.tau, isi);
+        a.g = g;
+        DIPS_HIP(h, dips::launch_series_grid(a, C, (int)h->p.chroma_filter, pf, isi, (uint32_t)q.blocks, s));
+        // the vecs the fast kernel leaves out (series_grid.hip): a partial
+        // last vec in the frame's last row that starts within 3 pixels of the
+        // frame's right edge would read past the frame's end.  Their <= 3
+        // pixels go into their cells by atomics (after the kernel's zeroing);
+        // cell edges decrease with the column, so at most three cells qualify
+        if (g.y + g.h == height) {
+            for (uint32_t c = g.cols; c-- > 0;) {
+                const dips::GridRect rc = dips::grid_cell_rect(g, g.rows - 1u, c);
+                if (rc.x + rc.w + 3u <= width) break;  // every vec of this and the earlier columns fits
+                const uint32_t x0 = rc.x + ((rc.w - 1u) & ~3u);  // its last vec
+                if (rc.w % 4u == 0u || x0 + 4u <= width) continue;
+                const dips::GridSpec tail{x0, height - 1u, rc.x + rc.w - x0, 1u, 1u, 1u};
+                dips_status st = launch_generic(tail, (g.rows - 1u) * g.cols + c);
+                if (st != DIPS_OK) return st;
+            }
+        }
+    } else {
+        dips_status st = launch_generic(g, 0u);
+        if (st != DIPS_OK) return st;
+    }
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    if (q.ok) DIPS_HIP(h, dips::launch_grid_reduce(a, C, cells, s));
+    return DIPS_OK;
+}
+
 // One timed launch of a read-only leg on the handle's stream: *ms = its
 // hipEvent duration (synchronous).
 template <typename Launch>
@@ -473,6 +641,60 @@ dips_status dips_diff_series_streamed(dips_handle* h, uint32_t width, uint32_t h
         if (st != DIPS_OK) return st;
         DIPS_HIP(h, hipMemcpyAsync(series, series_dev, sizeof(dips_series_entry) * (size_t)n_frames,
                                    hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_grid_cell(uint32_t width, uint32_t height, const uint32_t* roi, uint32_t rows, uint32_t cols,
+                           uint32_t row, uint32_t col, uint32_t* rect) {
+    return guard(nullptr, [&]() -> dips_status {
+        dips::GridSpec g{};
+        if (!rect || grid_spec(width, height, roi, rows, cols, &g) != nullptr || row >= rows || col >= cols)
+            return DIPS_ERR_INVALID;
+        const dips::GridRect r = dips::grid_cell_rect(g, row, col);
+        rect[0] = r.x;
+        rect[1] = r.y;
+        rect[2] = r.w;
+        rect[3] = r.h;
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_diff_series_grid(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames,
+                                  uint32_t n_frames, const uint8_t* ref, const uint32_t* roi, uint32_t rows,
+                                  uint32_t cols, dips_series_entry* cells) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!frames || !cells) return fail(h, DIPS_ERR_INVALID, "diff_series_grid: null argument");
+        dips::GridSpec g{};
+        if (const char* why = grid_spec(width, height, roi, rows, cols, &g))
+            return fail(h, DIPS_ERR_INVALID, std::string("diff_series_grid: ") + why);
+        const uint64_t n_cells = (uint64_t)rows * cols;
+        if (n_cells >= (1ull << 30) || n_cells * n_frames >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "diff_series_grid: n_frames * rows * cols must stay below 2^30 entries");
+        const int C = (int)h->p.format;
+        const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS)
+            return run_grid_device(h, width, height, frames, n_frames, ref ? ref : frames, g, cells, h->stream);
+        // host pointers: stage through HBM (synchronous call)
+        const size_t total = (size_t)fb * n_frames;
+        const size_t out_bytes = sizeof(dips_series_entry) * (size_t)(n_cells * n_frames);
+        DIPS_HIP(h, h->stage_frames.ensure(total));
+        DIPS_HIP(h, h->stage_series.ensure(out_bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, frames, total, hipMemcpyHostToDevice, h->stream));
+        const uint8_t* ref_dev = h->stage_frames.as<uint8_t>();
+        if (ref) {
+            DIPS_HIP(h, h->stage_ref.ensure(fb));
+            DIPS_HIP(h, hipMemcpyAsync(h->stage_ref.p, ref, fb, hipMemcpyHostToDevice, h->stream));
+            ref_dev = h->stage_ref.as<uint8_t>();
+        }
+        st = run_grid_device(h, width, height, h->stage_frames.as<uint8_t>(), n_frames, ref_dev, g,
+                             h->stage_series.as<dips_series_entry>(), h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(cells, h->stage_series.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

@@ -268,6 +268,32 @@ dips_status dips_diff_series_streamed(dips_handle *h, uint32_t width, uint32_t h
                                       const uint8_t *host_ref, dips_series_entry *series,
                                       uint32_t chunk_frames);
 
+/* The series resolved in space: a rows x cols grid over a region of interest.
+ *
+ * rect[4] = {x, y, w, h} of cell (row, col) of a rows x cols grid over roi
+ * (roi[4] = {x, y, w, h}; NULL = the whole width x height frame).
+ * Columns split [x, x+w) as dips_shard_range splits frames: column c covers
+ * [x + c*w/cols, x + (c+1)*w/cols); rows likewise.  Host only, no device.
+ * DIPS_ERR_INVALID for a null rect, rows or cols of 0 or beyond the roi's
+ * extent, an roi of zero extent or one that leaves the frame, row >= rows or
+ * col >= cols. */
+dips_status dips_grid_cell(uint32_t width, uint32_t height, const uint32_t *roi,
+                           uint32_t rows, uint32_t cols, uint32_t row, uint32_t col, uint32_t *rect);
+
+/* dips_diff_series per cell: cells[(t*rows + r)*cols + c] is exactly the entry
+ * dips_diff_series gives for the frames and ref cropped to that cell
+ * (n_frames*rows*cols entries, one read of the batch).  ref, the mode, the
+ * format, tau, chroma_filter and DIPS_FLAG_DEVICE_PTRS keep the meaning they
+ * have in dips_diff_series (device pointers: asynchronous on the handle's
+ * stream; host pointers: staged through HBM, synchronous; roi is always a
+ * host pointer, read before the call returns).  n_frames == 0 returns OK and
+ * writes nothing.  DIPS_ERR_INVALID for a null argument, the grid and roi
+ * errors of dips_grid_cell, and n_frames*rows*cols >= 2^30. */
+dips_status dips_diff_series_grid(dips_handle *h, uint32_t width, uint32_t height,
+                                  const uint8_t *frames, uint32_t n_frames, const uint8_t *ref,
+                                  const uint32_t *roi, uint32_t rows, uint32_t cols,
+                                  dips_series_entry *cells);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,
