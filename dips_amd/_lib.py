@@ -179,6 +179,7 @@ def load() -> ctypes.CDLL:
             "dips_diff_series": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, _u8p], st),
             "dips_grid_cell": ([u32, u32, P(u32), u32, u32, u32, u32, P(u32)], st),
             "dips_diff_series_grid": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, _vp], st),
+            "dips_diff_pixel_sums": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, _vp], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),
             "dips_diff_series_streamed": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, u32], st),
             "dips_synth_frames": ([_vp, u32, u32, u64, u64, u32, _u8p], st),

@@ -445,6 +445,31 @@ class GridSeries:
         return cls(a[..., 0].copy(), a[..., 1].copy(), a[..., 2].copy(), a[..., 3].copy())
 
 
+@dataclass
+class PixelSums:
+    """The difference series summed over time per pixel of a region
+    (dips_diff_pixel_sums): every field uint64 [h, w]."""
+    sad: np.ndarray
+    sj: np.ndarray
+    count: np.ndarray
+    si_fixed: np.ndarray
+
+    @property
+    def si(self) -> np.ndarray:
+        return np.ldexp(self.si_fixed.astype(np.float64), -32)
+
+    def as_array(self) -> np.ndarray:
+        """[h, w, 4]: sad, sj, count, si_fixed."""
+        return np.stack([self.sad, self.sj, self.count, self.si_fixed], axis=-1)
+
+    @classmethod
+    def from_array(cls, a: np.ndarray) -> "PixelSums":
+        a = np.asarray(a, dtype=np.uint64)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("pixel sums must be [h, w, 4]")
+        return cls(a[..., 0].copy(), a[..., 1].copy(), a[..., 2].copy(), a[..., 3].copy())
+
+
 def _roi_arg(roi):
     """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
     if roi is None:
@@ -614,6 +639,67 @@ class DiffSeriesOperator:
                 ref.data_ptr() if ref is not None else None, _roi_arg(roi), int(rows), int(cols),
                 cells_out.data_ptr()))
 
+    # -- the series summed over time per pixel (dips_diff_pixel_sums) ----------
+    def _region(self, roi, h: int, w: int) -> Tuple[int, int]:
+        """(rh, rw) of roi (None: the whole frame) for sizing the map; the
+        library checks that the region lies in the frame."""
+        if roi is None:
+            return h, w
+        _roi_arg(roi)
+        return int(roi[3]), int(roi[2])
+
+    def pixel_sums(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None,
+                   into: Optional[PixelSums] = None) -> PixelSums:
+        """Per pixel of roi = (x, y, w, h) (None: the whole frame) the sum
+        over the frames of the entry this operator gives for the frames and
+        ref cropped to that pixel.  `into`: a PixelSums of the same region to
+        add to (a clip in chunks: pass the previous chunk's last frame as ref
+        in per-frame mode, the same reference in overall mode)."""
+        frames = _as_u8(frames)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        if into is not None:
+            out = np.ascontiguousarray(into.as_array(), dtype=np.uint64)
+            if out.shape != (rh, rw, 4):
+                raise ValueError("into must hold the sums of the same region")
+        else:
+            out = np.zeros((rh, rw, 4), dtype=np.uint64)
+        rp = None
+        if ref is not None:
+            ref = _as_u8(ref)
+            if ref.size != h * w * int(self.fmt):
+                raise ValueError("ref must have the shape of one frame")
+            rp = ref.ctypes.data
+        self._host.check(self._host._lib.dips_diff_pixel_sums(
+            self._host.ptr, w, h, frames.ctypes.data if n else None, n, rp, _roi_arg(roi),
+            1 if into is not None else 0, out.ctypes.data))
+        return PixelSums.from_array(out)
+
+    def run_pixel_sums_device(self, frames, sums_out, roi=None, ref=None, accumulate: bool = False,
+                              stream=None) -> None:
+        """Asynchronous: frames / ref uint8 device tensors, sums_out an
+        8-byte device tensor of shape [h, w, 4] of the region, overwritten or
+        (accumulate) added to."""
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        if tuple(sums_out.shape) != (rh, rw, 4) or sums_out.element_size() != 8:
+            raise ValueError("sums_out must be an 8-byte tensor of shape [h, w, 4] of the region")
+        for t in (frames, sums_out, ref):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        import torch
+        for t in (frames, ref):
+            if t is not None and t.dtype != torch.uint8:
+                raise ValueError("frames and ref must be uint8 tensors")
+        if ref is not None and ref.numel() != h * w * int(self.fmt):
+            raise ValueError("ref must have the size of one frame")
+        lib = self._dev._lib
+        with _stream_of(self._dev, frames, stream):
+            self._dev.check(lib.dips_diff_pixel_sums(
+                self._dev.ptr, w, h, frames.data_ptr() if n else None, n,
+                ref.data_ptr() if ref is not None else None, _roi_arg(roi), 1 if accumulate else 0,
+                sums_out.data_ptr() if sums_out.numel() else None))
+
     # -- frame-range sharding (native: shard_abi.hip) -------------------------
     def run_sharded(self, comm, frames, n_total: int, series_local, series_all=None, ref=None,
                     ref_resident: bool = False, stream=None) -> None:
@@ -761,7 +847,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "grid_cell", "DiffSeriesOperator",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "grid_cell", "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",
 ]

@@ -151,6 +151,47 @@ struct GridGenericArgs {
     GridSpec g;
 };
 
+// series_pixels_kernel (series_pixels.hip): the series summed over time per
+// pixel of a region.  A tile = 64 * kUnrollPix vecs of the region in the grid
+// kernel's addressing (one cell = the region); a wave keeps its tile and
+// walks a part of the frames with per-pixel accumulators in registers.
+#ifndef DIPS_UNROLL_PIX
+#define DIPS_UNROLL_PIX 2
+#endif
+constexpr int kUnrollPix = DIPS_UNROLL_PIX;  // vecs per lane: 512 px / wave / frame
+constexpr uint32_t kPixMaxPart = 2048;       // frames per part the packed SJ | count << 20 word holds
+struct PixArgs {
+    const uint8_t* frames;   // n_frames * frame_bytes, contiguous
+    const uint8_t* ref0;     // overall: reference; per-frame: predecessor of frame 0
+    dips_series_entry* sums; // roi.w * roi.h entries
+    uint32_t frame_bytes;
+    uint32_t width;          // frame width in pixels (the row pitch)
+    uint32_t n_frames;
+    uint32_t n_tiles;
+    uint32_t n_waves;
+    uint32_t part_frames;    // frames per part (1 .. kPixMaxPart)
+    uint32_t out_mode;       // 0 store (one part), 1 load-add-store (one part, accumulate), 2 u64 atomic adds
+    float thr;               // series_threshold()
+    GridRect roi;
+};
+
+// pixels_generic_kernel: one thread per pixel of rect (inside the region)
+// walks the frames; sums[(py - roi_y) * roi_w + px - roi_x] written or added to.
+struct PixGenericArgs {
+    const uint8_t* frames;
+    const uint8_t* ref0;
+    dips_series_entry* sums;
+    uint64_t frame_bytes;
+    uint32_t width;
+    uint32_t n_frames;
+    uint32_t mode;
+    uint32_t chroma;
+    float tau;
+    uint32_t accumulate;
+    uint32_t roi_x, roi_y, roi_w;
+    GridRect rect;
+};
+
 struct SynthArgs {
     uint8_t* dst;
     uint64_t total_bytes;
@@ -331,6 +372,12 @@ hipError_t launch_series_grid(const GridArgs& a, int channels, int chroma, bool 
                               hipStream_t s);
 hipError_t launch_grid_reduce(const GridArgs& a, int channels, dips_series_entry* cells, hipStream_t s);
 hipError_t launch_grid_generic(const GridGenericArgs& a, int channels, hipStream_t s);
+// the per-pixel sums over time (series_pixels.hip): RGB8 / RGBA8 fast kernel
+// (isi as series_v2) and the any-format generic kernel
+const void* series_pixels_kernel_ptr(int channels, int chroma, bool per_frame, int isi);
+hipError_t launch_series_pixels(const PixArgs& a, int channels, int chroma, bool per_frame, int isi, uint32_t blocks,
+                                hipStream_t s);
+hipError_t launch_pixels_generic(const PixGenericArgs& a, int channels, hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 hipError_t launch_read_ceiling(const uint8_t* p, uint64_t bytes, uint32_t* out, hipStream_t s);
 // read-only walk in the RGB8 / RGBA8 series kernel's shape (vec_bytes 12 / 16, U = kUnrollV2Rgb / kUnrollV2)

@@ -23,6 +23,10 @@
 //            [--grid RxC [--roi x,y,w,h]] -> the series per cell of an R x C
 //            grid over the region (default: the whole frame) with
 //            dips_diff_series_grid: CSV t,row,col,sad,sj,count,si_fixed
+//            [--pixel-sums FILE [--roi x,y,w,h]] -> the series summed over
+//            time per pixel of the region with dips_diff_pixel_sums: FILE gets
+//            roi_h x roi_w x {sad, sj, count, si_fixed} little-endian u64,
+//            stdout one line with the region, the frames and the four totals
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -86,7 +90,7 @@ int usage() {
                  "       dips_raw alt IN.rgba W H OUT.rgba [--markers M1,M2,...] [--window N] [--textures N]\n"
                  "                [--ranks N [--transport loopback|rccl]]\n"
                  "       dips_raw series IN.raw W H rgb8|rgba8|gray8 [--mode overall|per-frame] [--tau T]\n"
-                 "                [--chunk N] [--grid RxC [--roi x,y,w,h]]\n"
+                 "                [--chunk N] [--grid RxC [--roi x,y,w,h]] [--pixel-sums FILE [--roi x,y,w,h]]\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -381,6 +385,7 @@ int run_series(int argc, char** argv) {
     uint32_t w = 0, h = 0, chunk = 0, rows = 0, cols = 0;
     uint32_t roi[4] = {0, 0, 0, 0};
     bool has_roi = false;
+    const char* pix_path = nullptr;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -400,6 +405,8 @@ int run_series(int argc, char** argv) {
             if (!parse_u32(argv[++i], &chunk)) return usage();
         } else if (a == "--grid" && has) {
             if (!parse_grid(argv[++i], &rows, &cols)) return usage();
+        } else if (a == "--pixel-sums" && has) {
+            pix_path = argv[++i];
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -407,7 +414,8 @@ int run_series(int argc, char** argv) {
             return usage();
         }
     }
-    if (has_roi && rows == 0) return usage();  // --roi belongs to --grid
+    if (has_roi && rows == 0 && !pix_path) return usage();  // --roi belongs to --grid or --pixel-sums
+    if (rows != 0 && pix_path) return usage();
     Mapped in;
     if (!in.open(argv[2])) {
         std::fprintf(stderr, "dips_raw: cannot map %s\n", argv[2]);
@@ -438,6 +446,38 @@ int run_series(int argc, char** argv) {
                         (unsigned long long)cells[i].count, (unsigned long long)cells[i].si_fixed);
         }
         dips_destroy(hd);
+        return 0;
+    }
+    if (pix_path) {
+        const uint32_t rw = has_roi ? roi[2] : w, rh = has_roi ? roi[3] : h;
+        // a region the library will refuse gets one entry: nothing is written to it
+        uint32_t rect[4];
+        const bool sane = dips_grid_cell(w, h, has_roi ? roi : nullptr, 1u, 1u, 0u, 0u, rect) == DIPS_OK &&
+                          (uint64_t)rw * rh < (1ull << 30);
+        std::vector<dips_series_entry> sums(sane ? (size_t)rw * rh : 1u);
+        st = dips_diff_pixel_sums(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, 0u, sums.data());
+        if (st != DIPS_OK) {
+            const int rc = lib_error(hd, "dips_diff_pixel_sums", st);
+            dips_destroy(hd);
+            return rc;
+        }
+        dips_destroy(hd);
+        // roi_h x roi_w x {sad, sj, count, si_fixed}, little-endian u64 (the host's own order on every target)
+        std::FILE* f = std::fopen(pix_path, "wb");
+        if (!f || std::fwrite(sums.data(), sizeof(dips_series_entry), sums.size(), f) != sums.size() ||
+            std::fclose(f) != 0) {
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", pix_path);
+            return 1;
+        }
+        unsigned long long tot[4] = {0, 0, 0, 0};
+        for (const dips_series_entry& e : sums) {
+            tot[0] += e.sad;
+            tot[1] += e.sj;
+            tot[2] += e.count;
+            tot[3] += e.si_fixed;
+        }
+        std::printf("pixel-sums roi=%u,%u,%u,%u frames=%u sad=%llu sj=%llu count=%llu si_fixed=%llu\n",
+                    has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, tot[0], tot[1], tot[2], tot[3]);
         return 0;
     }
     std::vector<dips_series_entry> series(n);

@@ -552,6 +552,142 @@ dips_status run_grid_device(dips_handle* h, uint32_t width, uint32_t height, con
     return DIPS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The per-pixel sums over time (dips_diff_pixel_sums; kernels in
+// series_pixels.hip)
+// ---------------------------------------------------------------------------
+
+struct PixGeom {
+    bool ok = false;
+    uint32_t part_frames = 0, parts = 0;
+    uint64_t n_tiles = 0, n_waves = 0, blocks = 0;
+};
+
+// Geometry of the fast per-pixel kernel: a persistent grid of occupancy x CUs
+// waves over items (frame part, tile).  One part -- every wave owns all
+// frames of its pixels and stores their entries -- unless the tiles are too
+// few to give every wave slot an item (then enough parts of >= 16 frames to
+// do so) or the batch exceeds the kPixMaxPart frames the in-register
+// accumulators hold; the parts then add their shares with atomics.  Refused
+// (the generic kernel runs): frames of 2^31 bytes or more, 2^28 frames.
+PixGeom pix_geometry(dips_handle* h, uint32_t width, uint32_t height, uint32_t n_frames, int C, bool pf, int isi,
+                     const dips::GridSpec& g) {
+    PixGeom q;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    if (fb >= (1ull << 31) || n_frames == 0 || n_frames >= (1u << 28)) return q;
+    const void* k = dips::series_pixels_kernel_ptr(C, (int)h->p.chroma_filter, pf, isi);
+    if (!k) return q;
+    const uint64_t vpt = 64u * (uint64_t)dips::kUnrollPix;  // vecs per tile
+    const uint64_t n_tiles = ((((uint64_t)g.w + 3) / 4) * g.h + vpt - 1) / vpt;
+    const uint64_t resident = waves_per_simd((uint64_t)occupancy_blocks(h, k), true) * (uint64_t)h->cu_count * 4u;
+    if (resident == 0 || n_tiles == 0 || n_tiles >= (1ull << 31)) return q;
+    // tiles that fill 98 % of the slots are left in one part (part_geometry's
+    // fill rule): a second part would buy 2 % and cost the memset and atomics
+    const uint64_t want = n_tiles * 100u >= resident * 98u ? 1u : (resident + n_tiles - 1) / n_tiles;
+    uint64_t parts = std::max<uint64_t>(1, std::min<uint64_t>(want, n_frames / 16u));
+    parts = std::max<uint64_t>(parts, ((uint64_t)n_frames + dips::kPixMaxPart - 1) / dips::kPixMaxPart);
+    q.part_frames = (uint32_t)((n_frames + parts - 1) / parts);
+    // DIPS_PIXEL_PART_FRAMES = 1 .. kPixMaxPart pins the part length (the
+    // tests run the accumulators at their limit on a small frame with it)
+    if (const char* pin = std::getenv("DIPS_PIXEL_PART_FRAMES")) {
+        const unsigned long L = std::strtoul(pin, nullptr, 10);
+        if (L >= 1 && L <= dips::kPixMaxPart) q.part_frames = (uint32_t)std::min<uint64_t>(L, n_frames);
+    }
+    q.parts = (uint32_t)((n_frames + q.part_frames - 1) / q.part_frames);
+    q.n_tiles = n_tiles;
+    q.n_waves = std::min((uint64_t)q.parts * n_tiles, resident);
+    q.blocks = (q.n_waves + 3) / 4;
+    q.ok = q.blocks < (1ull << 31);
+    return q;
+}
+
+// Run the per-pixel sums on device pointers, asynchronously on `s`.
+dips_status run_pixels_device(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames, uint32_t n_frames,
+                              const uint8_t* ref0, const dips::GridSpec& g, bool accumulate, dips_series_entry* sums,
+                              hipStream_t s) {
+    const int C = (int)h->p.format;
+    const bool pf = h->p.mode == DIPS_MODE_PER_FRAME;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    const int isi = series_isi_form(h);
+    PixGeom q;
+    // GRAY8 has no fast form; DIPS_FLAG_CROSSCHECK asks for the plain kernel
+    if (C != 1 && !(h->p.flags & DIPS_FLAG_FORCE_GENERIC) && !h->crosscheck())
+        q = pix_geometry(h, width, height, n_frames, C, pf, isi, g);
+    auto launch_generic = [&](const dips::GridRect& rect) -> dips_status {
+        dips::PixGenericArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.sums = sums;
+        a.frame_bytes = fb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.mode = h->p.mode;
+        a.chroma = C == 1 ? 0u : h->p.chroma_filter;
+        a.tau = h->p.tau;
+        a.accumulate = accumulate ? 1u : 0u;
+        a.roi_x = g.x;
+        a.roi_y = g.y;
+        a.roi_w = g.w;
+        a.rect = rect;
+        DIPS_HIP(h, dips::launch_pixels_generic(a, C, s));
+        return DIPS_OK;
+    };
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    if (q.ok) {
+        // several parts add with atomics: the map is zeroed in this earlier
+        // launch (waves of one launch are not ordered against each other)
+        if (q.parts > 1 && !accumulate)
+            DIPS_HIP(h, hipMemsetAsync(sums, 0, sizeof(dips_series_entry) * (size_t)g.w * g.h, s));
+        dips::PixArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.sums = sums;
+        a.frame_bytes = (uint32_t)fb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.n_tiles = (uint32_t)q.n_tiles;
+        a.n_waves = (uint32_t)q.n_waves;
+        a.part_frames = q.part_frames;
+        a.out_mode = q.parts > 1 ? 2u : (accumulate ? 1u : 0u);
+        a.thr = dips::series_threshold(C, h->p.tau, isi);
+        a.roi = dips::GridRect{g.x, g.y, g.w, g.h};
+        DIPS_HIP(h, dips::launch_series_pixels(a, C, (int)h->p.chroma_filter, pf, isi, (uint32_t)q.blocks, s));
+        // the vecs the fast kernel leaves out (series_pixels.hip): those that
+        // would read past the frame's end, i.e. that start within 3 pixels of
+        // it.  Vecs of a row are 4 pixels apart and a full vec ends inside its
+        // row, so that is at most the partial last vec of each of the region's
+        // last rows: one row for frames 3 or more pixels wide, up to 4 for
+        // narrower ones.  Their <= 3 pixels each are nobody else's
+        if (g.w % 4u != 0u) {
+            const uint32_t x0 = g.x + ((g.w - 1u) & ~3u);  // the last vec of a region row
+            const uint64_t npx = (uint64_t)width * height;
+            for (uint32_t r = g.h; r-- > 0 && g.h - r <= 4u;) {
+                if ((uint64_t)(g.y + r) * width + x0 + 4u <= npx) break;  // it and every earlier row fit
+                dips_status st = launch_generic(dips::GridRect{x0, g.y + r, g.x + g.w - x0, 1u});
+                if (st != DIPS_OK) return st;
+            }
+        }
+    } else {
+        dips_status st = launch_generic(dips::GridRect{g.x, g.y, g.w, g.h});
+        if (st != DIPS_OK) return st;
+    }
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    return DIPS_OK;
+}
+
 // One timed launch of a read-only leg on the handle's stream: *ms = its
 // hipEvent duration (synchronous).
 template <typename Launch>
@@ -695,6 +831,57 @@ dips_status dips_diff_series_grid(dips_handle* h, uint32_t width, uint32_t heigh
                              h->stage_series.as<dips_series_entry>(), h->stream);
         if (st != DIPS_OK) return st;
         DIPS_HIP(h, hipMemcpyAsync(cells, h->stage_series.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_diff_pixel_sums(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames,
+                                 uint32_t n_frames, const uint8_t* ref, const uint32_t* roi, uint32_t accumulate,
+                                 dips_series_entry* sums) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (!sums || (!frames && n_frames > 0)) return fail(h, DIPS_ERR_INVALID, "diff_pixel_sums: null argument");
+        dips::GridSpec g{};
+        if (const char* why = grid_spec(width, height, roi, 1u, 1u, &g))
+            return fail(h, DIPS_ERR_INVALID, std::string("diff_pixel_sums: ") + why);
+        const uint64_t n_px = (uint64_t)g.w * g.h;
+        if (n_px >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "diff_pixel_sums: the region must stay below 2^30 pixels");
+        const size_t out_bytes = sizeof(dips_series_entry) * (size_t)n_px;
+        const bool dev = (h->p.flags & DIPS_FLAG_DEVICE_PTRS) != 0;
+        if (n_frames == 0) {
+            // nothing to add: an overwriting call leaves zeros
+            if (accumulate != 0u) return DIPS_OK;
+            if (dev)
+                DIPS_HIP(h, hipMemsetAsync(sums, 0, out_bytes, h->stream));
+            else
+                std::memset(sums, 0, out_bytes);
+            return DIPS_OK;
+        }
+        const int C = (int)h->p.format;
+        const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+        if (dev)
+            return run_pixels_device(h, width, height, frames, n_frames, ref ? ref : frames, g, accumulate != 0u, sums,
+                                     h->stream);
+        // host pointers: stage through HBM (synchronous call)
+        const size_t total = (size_t)fb * n_frames;
+        DIPS_HIP(h, h->stage_frames.ensure(total));
+        DIPS_HIP(h, h->stage_series.ensure(out_bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, frames, total, hipMemcpyHostToDevice, h->stream));
+        if (accumulate != 0u)
+            DIPS_HIP(h, hipMemcpyAsync(h->stage_series.p, sums, out_bytes, hipMemcpyHostToDevice, h->stream));
+        const uint8_t* ref_dev = h->stage_frames.as<uint8_t>();
+        if (ref) {
+            DIPS_HIP(h, h->stage_ref.ensure(fb));
+            DIPS_HIP(h, hipMemcpyAsync(h->stage_ref.p, ref, fb, hipMemcpyHostToDevice, h->stream));
+            ref_dev = h->stage_ref.as<uint8_t>();
+        }
+        st = run_pixels_device(h, width, height, h->stage_frames.as<uint8_t>(), n_frames, ref_dev, g, accumulate != 0u,
+                               h->stage_series.as<dips_series_entry>(), h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(sums, h->stage_series.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

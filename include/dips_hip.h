@@ -294,6 +294,28 @@ dips_status dips_diff_series_grid(dips_handle *h, uint32_t width, uint32_t heigh
                                   const uint32_t *roi, uint32_t rows, uint32_t cols,
                                   dips_series_entry *cells);
 
+/* The series summed over time per pixel of a region of interest (the
+ * activity map of a clip): sums[(py - y)*w + (px - x)] is the sum over t of
+ * the entry dips_diff_series gives for frame t when frames and reference are
+ * cropped to the single pixel (px, py) -- equivalently the sum over t of
+ * dips_diff_series_grid's cells with rows = h, cols = w.  roi_w * roi_h
+ * entries; every field an exact u64 sum.  Mode, format, tau, chroma_filter,
+ * ref and DIPS_FLAG_DEVICE_PTRS as in dips_diff_series (device pointers:
+ * asynchronous on the handle's stream; host pointers: staged through HBM,
+ * synchronous; roi is always a host pointer, read before the call returns).
+ * accumulate == 0: sums is overwritten (zero-filled when n_frames == 0);
+ * accumulate != 0: the batch's sums are added to what sums holds (nothing is
+ * written when n_frames == 0) -- a clip longer than memory goes chunk by
+ * chunk, with the previous chunk's last frame as ref in 'per-frame' mode or
+ * the same reference in 'overall' mode, and per-rank maps of a sharded clip
+ * are combined the same way.  DIPS_ERR_INVALID for null frames with
+ * n_frames > 0, null sums, the roi errors of dips_grid_cell (at rows = cols
+ * = 1) and a region of 2^30 pixels or more. */
+dips_status dips_diff_pixel_sums(dips_handle *h, uint32_t width, uint32_t height,
+                                 const uint8_t *frames, uint32_t n_frames, const uint8_t *ref,
+                                 const uint32_t *roi, uint32_t accumulate,
+                                 dips_series_entry *sums);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,
