@@ -180,6 +180,8 @@ def load() -> ctypes.CDLL:
             "dips_grid_cell": ([u32, u32, P(u32), u32, u32, u32, u32, P(u32)], st),
             "dips_diff_series_grid": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, _vp], st),
             "dips_diff_pixel_sums": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, _vp], st),
+            "dips_mask_row_bytes": ([u32], u32),
+            "dips_diff_change_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), _u8p], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),
             "dips_diff_series_streamed": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, u32], st),
             "dips_synth_frames": ([_vp, u32, u32, u64, u64, u32, _u8p], st),

@@ -470,6 +470,39 @@ class PixelSums:
         return cls(a[..., 0].copy(), a[..., 1].copy(), a[..., 2].copy(), a[..., 3].copy())
 
 
+def mask_row_bytes(width: int) -> int:
+    """Bytes of one row of a change mask of a region `width` pixels wide
+    (dips_mask_row_bytes): 4 * ceil(width / 32)."""
+    if int(width) < 0 or int(width) > 0xFFFFFFFF:
+        raise ValueError("width must be a non-negative 32-bit integer")
+    return int(_lib.load().dips_mask_row_bytes(int(width)))
+
+
+@dataclass
+class ChangeMask:
+    """The per-frame change mask of a region (dips_diff_change_mask): `bits`
+    uint8 [n, h, row_bytes], one bit per pixel, bit i of a row = bit (i & 7)
+    of byte (i >> 3), pad bits 0; `width` the region's width in pixels."""
+    bits: np.ndarray
+    width: int
+
+    def unpack(self) -> np.ndarray:
+        """bool [n, h, w]: whether pixel (i, j) changed in frame t."""
+        return np.unpackbits(self.bits, axis=-1, bitorder="little")[..., :self.width].astype(bool)
+
+    def counts(self) -> np.ndarray:
+        """uint64 [n]: changed pixels per frame (the series' count)."""
+        n = self.bits.shape[0]
+        return np.unpackbits(self.bits.reshape(n, -1), axis=1).sum(axis=1, dtype=np.uint64)
+
+    @classmethod
+    def from_array(cls, a: np.ndarray, width: int) -> "ChangeMask":
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim != 3 or int(width) < 0 or a.shape[2] != 4 * ((int(width) + 31) // 32):
+            raise ValueError("mask must be [n, h, 4 * ceil(width / 32)] bytes")
+        return cls(a, int(width))
+
+
 def _roi_arg(roi):
     """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
     if roi is None:
@@ -700,6 +733,52 @@ class DiffSeriesOperator:
                 ref.data_ptr() if ref is not None else None, _roi_arg(roi), 1 if accumulate else 0,
                 sums_out.data_ptr() if sums_out.numel() else None))
 
+    # -- the per-frame change mask (dips_diff_change_mask) -------------------
+    def change_mask(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None) -> ChangeMask:
+        """One bit per pixel of roi = (x, y, w, h) (None: the whole frame) and
+        frame: whether this operator counts the pixel as changed in that
+        frame (the count of the series of the 1x1 crop).  A clip in chunks:
+        pass the previous chunk's last frame as ref in per-frame mode, the
+        same reference in overall mode."""
+        frames = _as_u8(frames)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        out = np.zeros((n, rh, 4 * ((rw + 31) // 32)), dtype=np.uint8)
+        rp = None
+        if ref is not None:
+            ref = _as_u8(ref)
+            if ref.size != h * w * int(self.fmt):
+                raise ValueError("ref must have the shape of one frame")
+            rp = ref.ctypes.data
+        self._host.check(self._host._lib.dips_diff_change_mask(
+            self._host.ptr, w, h, frames.ctypes.data if n else None, n, rp, _roi_arg(roi),
+            out.ctypes.data if out.size else None))
+        return ChangeMask(out, rw)
+
+    def run_change_mask_device(self, frames, mask_out, roi=None, ref=None, stream=None) -> None:
+        """Asynchronous: frames / ref uint8 device tensors, mask_out a uint8
+        device tensor of shape [N, h, row_bytes] of the region (4-byte
+        aligned), every byte of which is written."""
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        if tuple(mask_out.shape) != (n, rh, 4 * ((rw + 31) // 32)):
+            raise ValueError("mask_out must be a uint8 tensor of shape [N, h, 4 * ceil(w / 32)] of the region")
+        for t in (frames, mask_out, ref):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        import torch
+        for t in (frames, mask_out, ref):
+            if t is not None and t.dtype != torch.uint8:
+                raise ValueError("frames, ref and mask_out must be uint8 tensors")
+        if ref is not None and ref.numel() != h * w * int(self.fmt):
+            raise ValueError("ref must have the size of one frame")
+        lib = self._dev._lib
+        with _stream_of(self._dev, frames, stream):
+            self._dev.check(lib.dips_diff_change_mask(
+                self._dev.ptr, w, h, frames.data_ptr() if n else None, n,
+                ref.data_ptr() if ref is not None else None, _roi_arg(roi),
+                mask_out.data_ptr() if mask_out.numel() else None))
+
     # -- frame-range sharding (native: shard_abi.hip) -------------------------
     def run_sharded(self, comm, frames, n_total: int, series_local, series_all=None, ref=None,
                     ref_resident: bool = False, stream=None) -> None:
@@ -847,7 +926,8 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "grid_cell", "DiffSeriesOperator",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "ChangeMask", "mask_row_bytes", "grid_cell",
+    "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",
 ]

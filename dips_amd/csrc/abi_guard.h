@@ -56,6 +56,8 @@ R on_exception(dips_status st) noexcept {
         return;
     } else if constexpr (std::is_same_v<R, dips_status> || std::is_same_v<R, int>) {
         return static_cast<R>(st);
+    } else if constexpr (std::is_unsigned_v<R>) {
+        return 0;  // a size (dips_mask_row_bytes): no valid region has 0 bytes
     } else if constexpr (std::is_floating_point_v<R>) {
         return std::numeric_limits<R>::quiet_NaN();
     } else if constexpr (std::is_same_v<R, const char*>) {

@@ -192,6 +192,47 @@ struct PixGenericArgs {
     GridRect rect;
 };
 
+// series_mask_kernel (series_mask.hip): the per-frame change mask, one bit
+// per pixel of a region.  The vecs of a region row are padded to a multiple
+// of 8 (one mask word = 8 vecs = 32 pixels), (row, vec) flattened over the
+// padded rows: flat vec i belongs to flat mask word i >> 3 of the frame.
+#ifndef DIPS_UNROLL_MASK
+#define DIPS_UNROLL_MASK 4
+#endif
+constexpr int kUnrollMask = DIPS_UNROLL_MASK;  // vecs per lane: 1024 px / wave / frame
+struct MaskArgs {
+    const uint8_t* frames;   // n_frames * frame_bytes, contiguous
+    const uint8_t* ref0;     // overall: reference; per-frame: predecessor of frame 0
+    uint8_t* mask;           // n_frames * mask_frame_bytes, 4-byte aligned
+    uint32_t frame_bytes;
+    uint32_t mask_frame_bytes;  // roi.h * 4 * ceil(roi.w / 32)
+    uint32_t width;          // frame width in pixels (the row pitch)
+    uint32_t n_frames;
+    uint32_t n_tiles;
+    uint32_t n_waves;
+    uint32_t part_frames;    // frames per part (>= 1)
+    float thr;               // series_threshold(C, tau, 0)
+    GridRect roi;
+};
+
+// mask_generic_kernel: one thread per (frame, mask word) of rows [row0, row0
+// + n_rows) x words [word0, word0 + n_words) of the region's mask, frames
+// [t0, t0 + n_frames) of the batch.
+struct MaskGenericArgs {
+    const uint8_t* frames;
+    const uint8_t* ref0;
+    uint8_t* mask;
+    uint64_t frame_bytes;
+    uint64_t mask_frame_bytes;
+    uint32_t width;
+    uint32_t t0, n_frames;
+    uint32_t mode;
+    uint32_t chroma;
+    float tau;
+    uint32_t row0, n_rows, word0, n_words;
+    GridRect roi;
+};
+
 struct SynthArgs {
     uint8_t* dst;
     uint64_t total_bytes;
@@ -378,6 +419,12 @@ const void* series_pixels_kernel_ptr(int channels, int chroma, bool per_frame, i
 hipError_t launch_series_pixels(const PixArgs& a, int channels, int chroma, bool per_frame, int isi, uint32_t blocks,
                                 hipStream_t s);
 hipError_t launch_pixels_generic(const PixGenericArgs& a, int channels, hipStream_t s);
+// the per-frame change mask (series_mask.hip): RGB8 / RGBA8 fast kernel (one
+// intensity form for every tau) and the any-format generic kernel
+const void* series_mask_kernel_ptr(int channels, int chroma, bool per_frame);
+hipError_t launch_series_mask(const MaskArgs& a, int channels, int chroma, bool per_frame, uint32_t blocks,
+                              hipStream_t s);
+hipError_t launch_mask_generic(const MaskGenericArgs& a, int channels, hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 hipError_t launch_read_ceiling(const uint8_t* p, uint64_t bytes, uint32_t* out, hipStream_t s);
 // read-only walk in the RGB8 / RGBA8 series kernel's shape (vec_bytes 12 / 16, U = kUnrollV2Rgb / kUnrollV2)

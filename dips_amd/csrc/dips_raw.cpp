@@ -27,6 +27,11 @@
 //            time per pixel of the region with dips_diff_pixel_sums: FILE gets
 //            roi_h x roi_w x {sad, sj, count, si_fixed} little-endian u64,
 //            stdout one line with the region, the frames and the four totals
+//            [--mask FILE [--roi x,y,w,h]] -> the per-frame change mask of the
+//            region with dips_diff_change_mask: FILE gets frames x roi_h x
+//            row_bytes bytes (one bit per pixel, LSB first, rows padded to
+//            32 bits), stdout one line with the region, the frames, the row
+//            bytes and the number of set bits
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -91,6 +96,7 @@ int usage() {
                  "                [--ranks N [--transport loopback|rccl]]\n"
                  "       dips_raw series IN.raw W H rgb8|rgba8|gray8 [--mode overall|per-frame] [--tau T]\n"
                  "                [--chunk N] [--grid RxC [--roi x,y,w,h]] [--pixel-sums FILE [--roi x,y,w,h]]\n"
+                 "                [--mask FILE [--roi x,y,w,h]]\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -386,6 +392,7 @@ int run_series(int argc, char** argv) {
     uint32_t roi[4] = {0, 0, 0, 0};
     bool has_roi = false;
     const char* pix_path = nullptr;
+    const char* mask_path = nullptr;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -407,6 +414,8 @@ int run_series(int argc, char** argv) {
             if (!parse_grid(argv[++i], &rows, &cols)) return usage();
         } else if (a == "--pixel-sums" && has) {
             pix_path = argv[++i];
+        } else if (a == "--mask" && has) {
+            mask_path = argv[++i];
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -414,8 +423,8 @@ int run_series(int argc, char** argv) {
             return usage();
         }
     }
-    if (has_roi && rows == 0 && !pix_path) return usage();  // --roi belongs to --grid or --pixel-sums
-    if (rows != 0 && pix_path) return usage();
+    if (has_roi && rows == 0 && !pix_path && !mask_path) return usage();  // --roi belongs to --grid, --pixel-sums or --mask
+    if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) > 1) return usage();
     Mapped in;
     if (!in.open(argv[2])) {
         std::fprintf(stderr, "dips_raw: cannot map %s\n", argv[2]);
@@ -478,6 +487,34 @@ int run_series(int argc, char** argv) {
         }
         std::printf("pixel-sums roi=%u,%u,%u,%u frames=%u sad=%llu sj=%llu count=%llu si_fixed=%llu\n",
                     has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, tot[0], tot[1], tot[2], tot[3]);
+        return 0;
+    }
+    if (mask_path) {
+        const uint32_t rw = has_roi ? roi[2] : w, rh = has_roi ? roi[3] : h;
+        // a region the library will refuse gets one byte: nothing is written to it
+        uint32_t rect[4];
+        const bool sane = dips_grid_cell(w, h, has_roi ? roi : nullptr, 1u, 1u, 0u, 0u, rect) == DIPS_OK &&
+                          (uint64_t)rw * rh < (1ull << 30);
+        const uint32_t row_bytes = dips_mask_row_bytes(rw);
+        std::vector<uint8_t> mask(sane ? (size_t)n * rh * row_bytes : 1u);
+        st = dips_diff_change_mask(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, mask.data());
+        if (st != DIPS_OK) {
+            const int rc = lib_error(hd, "dips_diff_change_mask", st);
+            dips_destroy(hd);
+            return rc;
+        }
+        dips_destroy(hd);
+        if (n == 0) mask.clear();
+        // frames x roi_h x row_bytes, bit i of a row = bit (i & 7) of byte (i >> 3)
+        std::FILE* f = std::fopen(mask_path, "wb");
+        if (!f || std::fwrite(mask.data(), 1, mask.size(), f) != mask.size() || std::fclose(f) != 0) {
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", mask_path);
+            return 1;
+        }
+        unsigned long long set = 0;
+        for (const uint8_t b : mask) set += (unsigned long long)__builtin_popcount(b);
+        std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu\n", has_roi ? roi[0] : 0u,
+                    has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
         return 0;
     }
     std::vector<dips_series_entry> series(n);

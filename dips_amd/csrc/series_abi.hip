@@ -688,6 +688,150 @@ dips_status run_pixels_device(dips_handle* h, uint32_t width, uint32_t height, c
     return DIPS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The per-frame change mask (dips_diff_change_mask; kernels in
+// series_mask.hip)
+// ---------------------------------------------------------------------------
+
+uint64_t mask_words_per_row(uint32_t roi_w) { return ((uint64_t)roi_w + 31u) / 32u; }
+
+struct MaskGeom {
+    bool ok = false;
+    uint32_t part_frames = 0, parts = 0;
+    uint64_t n_tiles = 0, n_waves = 0, blocks = 0;
+};
+
+// Geometry of the fast mask kernel: a persistent grid of occupancy x CUs
+// waves over items (frame part, tile), a tile = 64 * kUnrollMask vecs of the
+// region rows padded to whole mask words.  Parts as the grid cuts them: as
+// part_geometry cuts them, or for the batches it leaves alone as many parts
+// of >= 16 frames as give every wave slot an item; no upper cap on a part
+// (nothing is accumulated), and every word has one writer whatever the part
+// count.  Refused
+// (the generic kernel runs): frames of 2^31 bytes or more, 2^28 frames,
+// regions whose padded rows hold 2^31 vecs or more.
+MaskGeom mask_geometry(dips_handle* h, uint32_t width, uint32_t height, uint32_t n_frames, int C, bool pf,
+                       const dips::GridSpec& g) {
+    MaskGeom q;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    if (fb >= (1ull << 31) || n_frames == 0 || n_frames >= (1u << 28)) return q;
+    const void* k = dips::series_mask_kernel_ptr(C, (int)h->p.chroma_filter, pf);
+    if (!k) return q;
+    const uint64_t vpt = 64u * (uint64_t)dips::kUnrollMask;  // vecs per tile
+    const uint64_t nvec8 = 8u * mask_words_per_row(g.w) * g.h;
+    if (nvec8 >= (1ull << 31)) return q;
+    const uint64_t n_tiles = (nvec8 + vpt - 1) / vpt;
+    const uint64_t resident = waves_per_simd((uint64_t)occupancy_blocks(h, k), true) * (uint64_t)h->cu_count * 4u;
+    if (resident == 0 || n_tiles == 0) return q;
+    FastGeom f;
+    f.n_tiles = n_tiles;
+    part_geometry(f, n_frames, resident);
+    if (f.part_frames != 0) {
+        q.part_frames = f.part_frames;
+        q.parts = (uint32_t)((n_frames + q.part_frames - 1) / q.part_frames);
+        q.n_waves = f.n_waves;
+    } else {
+        const uint64_t want = (resident + n_tiles - 1) / n_tiles;
+        const uint64_t parts = std::max<uint64_t>(1, std::min<uint64_t>(want, n_frames / 16u));
+        q.part_frames = (uint32_t)((n_frames + parts - 1) / parts);
+        q.parts = (uint32_t)((n_frames + q.part_frames - 1) / q.part_frames);
+        q.n_waves = std::min((uint64_t)q.parts * n_tiles, resident);
+    }
+    q.n_tiles = n_tiles;
+    q.blocks = (q.n_waves + 3) / 4;
+    q.ok = q.blocks < (1ull << 31);
+    return q;
+}
+
+// Run the change mask on device pointers, asynchronously on `s`.
+dips_status run_mask_device(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames, uint32_t n_frames,
+                            const uint8_t* ref0, const dips::GridSpec& g, uint8_t* mask, hipStream_t s) {
+    const int C = (int)h->p.format;
+    const bool pf = h->p.mode == DIPS_MODE_PER_FRAME;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    const uint64_t wpr = mask_words_per_row(g.w);
+    const uint64_t mfb = wpr * g.h * 4u;
+    MaskGeom q;
+    // GRAY8 has no fast form; DIPS_FLAG_CROSSCHECK asks for the plain kernel
+    if (C != 1 && !(h->p.flags & DIPS_FLAG_FORCE_GENERIC) && !h->crosscheck())
+        q = mask_geometry(h, width, height, n_frames, C, pf, g);
+    auto launch_generic = [&](uint32_t row0, uint32_t n_rows, uint32_t word0, uint32_t n_words) -> dips_status {
+        dips::MaskGenericArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.mask = mask;
+        a.frame_bytes = fb;
+        a.mask_frame_bytes = mfb;
+        a.width = width;
+        a.t0 = 0u;
+        a.n_frames = n_frames;
+        a.mode = h->p.mode;
+        a.chroma = C == 1 ? 0u : h->p.chroma_filter;
+        a.tau = h->p.tau;
+        a.row0 = row0;
+        a.n_rows = n_rows;
+        a.word0 = word0;
+        a.n_words = n_words;
+        a.roi = dips::GridRect{g.x, g.y, g.w, g.h};
+        DIPS_HIP(h, dips::launch_mask_generic(a, C, s));
+        return DIPS_OK;
+    };
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    if (q.ok) {
+        dips::MaskArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.mask = mask;
+        a.frame_bytes = (uint32_t)fb;
+        a.mask_frame_bytes = (uint32_t)mfb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.n_tiles = (uint32_t)q.n_tiles;
+        a.n_waves = (uint32_t)q.n_waves;
+        a.part_frames = q.part_frames;
+        a.thr = dips::series_threshold(C, h->p.tau, 0);
+        a.roi = dips::GridRect{g.x, g.y, g.w, g.h};
+        DIPS_HIP(h, dips::launch_series_mask(a, C, (int)h->p.chroma_filter, pf, (uint32_t)q.blocks, s));
+        // the vecs the fast kernel leaves out (series_mask.hip): those that
+        // would read past the frame's end, i.e. the partial last vec of the
+        // region's last rows where it starts within 3 pixels of the frame's
+        // end (run_pixels_device's test): one row for frames 3 or more pixels
+        // wide, up to 4 for narrower ones.  The fast kernel stored the word
+        // that holds such a vec with zeros in its place; this later launch
+        // recomputes and stores the whole word, so no two launches race for
+        // it and nothing is ORed into memory
+        if (g.w % 4u != 0u) {
+            const uint32_t x0 = g.x + ((g.w - 1u) & ~3u);  // the last vec of a region row
+            const uint64_t npx = (uint64_t)width * height;
+            for (uint32_t r = g.h; r-- > 0 && g.h - r <= 4u;) {
+                if ((uint64_t)(g.y + r) * width + x0 + 4u <= npx) break;  // it and every earlier row fit
+                dips_status st = launch_generic(r, 1u, (g.w - 1u) >> 5, 1u);
+                if (st != DIPS_OK) return st;
+            }
+        }
+    } else {
+        if ((uint64_t)g.h * wpr >= (1ull << 31))
+            return fail(h, DIPS_ERR_INVALID, "diff_change_mask: region too large for the generic kernel");
+        dips_status st = launch_generic(0u, g.h, 0u, (uint32_t)wpr);
+        if (st != DIPS_OK) return st;
+    }
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    return DIPS_OK;
+}
+
 // One timed launch of a read-only leg on the handle's stream: *ms = its
 // hipEvent duration (synchronous).
 template <typename Launch>
@@ -882,6 +1026,50 @@ dips_status dips_diff_pixel_sums(dips_handle* h, uint32_t width, uint32_t height
                                h->stage_series.as<dips_series_entry>(), h->stream);
         if (st != DIPS_OK) return st;
         DIPS_HIP(h, hipMemcpyAsync(sums, h->stage_series.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+uint32_t dips_mask_row_bytes(uint32_t roi_w) {
+    return guard(nullptr, [&]() -> uint32_t { return (uint32_t)(4u * mask_words_per_row(roi_w)); });
+}
+
+dips_status dips_diff_change_mask(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames,
+                                  uint32_t n_frames, const uint8_t* ref, const uint32_t* roi, uint8_t* mask) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!frames || !mask) return fail(h, DIPS_ERR_INVALID, "diff_change_mask: null argument");
+        dips::GridSpec g{};
+        if (const char* why = grid_spec(width, height, roi, 1u, 1u, &g))
+            return fail(h, DIPS_ERR_INVALID, std::string("diff_change_mask: ") + why);
+        if ((uint64_t)g.w * g.h >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "diff_change_mask: the region must stay below 2^30 pixels");
+        const int C = (int)h->p.format;
+        const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            if (((uintptr_t)mask & 3u) != 0)
+                return fail(h, DIPS_ERR_INVALID, "diff_change_mask: the device mask must be 4-byte aligned");
+            return run_mask_device(h, width, height, frames, n_frames, ref ? ref : frames, g, mask, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call)
+        const size_t total = (size_t)fb * n_frames;
+        const size_t out_bytes = (size_t)(4u * mask_words_per_row(g.w) * g.h) * n_frames;
+        DIPS_HIP(h, h->stage_frames.ensure(total));
+        DIPS_HIP(h, h->stage_map.ensure(out_bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, frames, total, hipMemcpyHostToDevice, h->stream));
+        const uint8_t* ref_dev = h->stage_frames.as<uint8_t>();
+        if (ref) {
+            DIPS_HIP(h, h->stage_ref.ensure(fb));
+            DIPS_HIP(h, hipMemcpyAsync(h->stage_ref.p, ref, fb, hipMemcpyHostToDevice, h->stream));
+            ref_dev = h->stage_ref.as<uint8_t>();
+        }
+        st = run_mask_device(h, width, height, h->stage_frames.as<uint8_t>(), n_frames, ref_dev, g,
+                             h->stage_map.as<uint8_t>(), h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(mask, h->stage_map.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

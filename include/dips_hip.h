@@ -316,6 +316,41 @@ dips_status dips_diff_pixel_sums(dips_handle *h, uint32_t width, uint32_t height
                                  const uint32_t *roi, uint32_t accumulate,
                                  dips_series_entry *sums);
 
+/* Bytes of one row of a change mask of a region roi_w pixels wide:
+ * 4 * ((roi_w + 31) / 32).  Host only, no device. */
+uint32_t dips_mask_row_bytes(uint32_t roi_w);
+
+/* The per-frame change mask of a region of interest, one bit per pixel (the
+ * "difference pixels" themselves): for roi = {x, y, w, h} (NULL = the whole
+ * frame), frame t and region pixel (i, j),
+ *   bit(t, j, i) = the count field of the entry dips_diff_series gives for
+ *                  frame t when frames and reference are cropped to the
+ *                  single pixel (x + i, y + j)
+ * -- 0 or 1, equal to dips_diff_series_grid's cells[t] with rows = h and
+ * cols = w.  The compare is strict (an unchanged pixel is 0 even at tau = 0),
+ * and in 'per-frame' mode with ref == NULL frame 0 is all zero.  The
+ * reference has no counterpart: it keeps |dI| per pixel only inside its
+ * shader (dips_shader.wgsl:64-82) and returns the coloured visualisation.
+ * Layout of mask: a row is dips_mask_row_bytes(w) bytes, a frame h rows,
+ * frames contiguous (n_frames * h * row_bytes bytes); bit i of a row is bit
+ * (i & 7) of byte (i >> 3), i.e. bit (i & 31) of the little-endian u32 word
+ * (i >> 5).  The pad bits of a row's last word are written as 0 and the call
+ * writes every byte of the mask: the caller need not clear it.
+ * Mode, format, tau, chroma_filter, ref and DIPS_FLAG_DEVICE_PTRS as in
+ * dips_diff_series (device pointers: asynchronous on the handle's stream,
+ * mask 4-byte aligned, frames and ref at any byte alignment; host pointers:
+ * staged through HBM, synchronous, any alignment; roi is always a host
+ * pointer, read before the call returns).  n_frames == 0 returns OK and
+ * writes nothing.  A clip longer than memory goes chunk by chunk with no
+ * further machinery: in 'per-frame' mode pass the previous chunk's last
+ * frame as ref, in 'overall' mode the same reference each time.
+ * DIPS_ERR_INVALID for null frames or mask with n_frames > 0, a device mask
+ * that is not 4-byte aligned, the roi errors of dips_grid_cell (at rows =
+ * cols = 1) and a region of 2^30 pixels or more. */
+dips_status dips_diff_change_mask(dips_handle *h, uint32_t width, uint32_t height,
+                                  const uint8_t *frames, uint32_t n_frames, const uint8_t *ref,
+                                  const uint32_t *roi, uint8_t *mask);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,
