@@ -41,6 +41,8 @@ FMT_RGBA8 = 4
 MODE_OVERALL = 0
 MODE_PER_FRAME = 1
 
+TIME_NONE = 0xFFFFFFFF  # DIPS_TIME_NONE
+
 COMM_ID_BYTES = 128
 COMM_RCCL = 1
 COMM_LOOPBACK = 2
@@ -182,6 +184,7 @@ def load() -> ctypes.CDLL:
             "dips_diff_pixel_sums": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, _vp], st),
             "dips_mask_row_bytes": ([u32], u32),
             "dips_diff_change_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), _u8p], st),
+            "dips_diff_pixel_times": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, _vp], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),
             "dips_diff_series_streamed": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, u32], st),
             "dips_synth_frames": ([_vp, u32, u32, u64, u64, u32, _u8p], st),

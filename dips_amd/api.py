@@ -503,6 +503,32 @@ class ChangeMask:
         return cls(a, int(width))
 
 
+@dataclass
+class PixelTimes:
+    """The change times per pixel of a region (dips_diff_pixel_times): every
+    field uint32 [h, w].  `first` / `last`: the global index of the first /
+    last frame in which the pixel changed (NONE: it never did); `run_max`:
+    the longest run of consecutive frames in which it changed; `run_cur`:
+    the run that ends at the newest frame folded."""
+    first: np.ndarray
+    last: np.ndarray
+    run_max: np.ndarray
+    run_cur: np.ndarray
+
+    NONE = _lib.TIME_NONE
+
+    def as_array(self) -> np.ndarray:
+        """[4, h, w]: first, last, run_max, run_cur (the C ABI's planes)."""
+        return np.stack([self.first, self.last, self.run_max, self.run_cur], axis=0)
+
+    @classmethod
+    def from_array(cls, a: np.ndarray) -> "PixelTimes":
+        a = np.asarray(a, dtype=np.uint32)
+        if a.ndim != 3 or a.shape[0] != 4:
+            raise ValueError("pixel times must be [4, h, w]")
+        return cls(a[0].copy(), a[1].copy(), a[2].copy(), a[3].copy())
+
+
 def _roi_arg(roi):
     """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
     if roi is None:
@@ -779,6 +805,65 @@ class DiffSeriesOperator:
                 ref.data_ptr() if ref is not None else None, _roi_arg(roi),
                 mask_out.data_ptr() if mask_out.numel() else None))
 
+    # -- the change times per pixel (dips_diff_pixel_times) --------------------
+    def pixel_times(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None, t0: int = 0,
+                    into: Optional[PixelTimes] = None) -> PixelTimes:
+        """Per pixel of roi = (x, y, w, h) (None: the whole frame) the index
+        of the first and of the last frame whose change_mask bit is set, the
+        longest run of set bits and the run ending at the last frame; frame
+        t of the batch has the global index t0 + t.  `into`: a PixelTimes of
+        the same region to fold onto (a clip in chunks: t0 = the frames
+        folded so far, and the previous chunk's last frame as ref in
+        per-frame mode, the same reference in overall mode)."""
+        frames = _as_u8(frames)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        if int(t0) < 0 or int(t0) > 0xFFFFFFFF:
+            raise ValueError("t0 must be a non-negative 32-bit integer")
+        if into is not None:
+            out = np.ascontiguousarray(into.as_array(), dtype=np.uint32)
+            if out.shape != (4, rh, rw):
+                raise ValueError("into must hold the times of the same region")
+        else:
+            out = np.zeros((4, rh, rw), dtype=np.uint32)
+        rp = None
+        if ref is not None:
+            ref = _as_u8(ref)
+            if ref.size != h * w * int(self.fmt):
+                raise ValueError("ref must have the shape of one frame")
+            rp = ref.ctypes.data
+        self._host.check(self._host._lib.dips_diff_pixel_times(
+            self._host.ptr, w, h, frames.ctypes.data if n else None, n, rp, _roi_arg(roi), int(t0),
+            1 if into is not None else 0, out.ctypes.data))
+        return PixelTimes.from_array(out)
+
+    def run_pixel_times_device(self, frames, times_out, roi=None, ref=None, t0: int = 0, accumulate: bool = False,
+                               stream=None) -> None:
+        """Asynchronous: frames / ref uint8 device tensors, times_out a
+        4-byte device tensor of shape [4, h, w] of the region (4-byte
+        aligned), overwritten or (accumulate) folded onto."""
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        if tuple(times_out.shape) != (4, rh, rw) or times_out.element_size() != 4:
+            raise ValueError("times_out must be a 4-byte tensor of shape [4, h, w] of the region")
+        if int(t0) < 0 or int(t0) > 0xFFFFFFFF:
+            raise ValueError("t0 must be a non-negative 32-bit integer")
+        for t in (frames, times_out, ref):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        import torch
+        for t in (frames, ref):
+            if t is not None and t.dtype != torch.uint8:
+                raise ValueError("frames and ref must be uint8 tensors")
+        if ref is not None and ref.numel() != h * w * int(self.fmt):
+            raise ValueError("ref must have the size of one frame")
+        lib = self._dev._lib
+        with _stream_of(self._dev, frames, stream):
+            self._dev.check(lib.dips_diff_pixel_times(
+                self._dev.ptr, w, h, frames.data_ptr() if n else None, n,
+                ref.data_ptr() if ref is not None else None, _roi_arg(roi), int(t0), 1 if accumulate else 0,
+                times_out.data_ptr() if times_out.numel() else None))
+
     # -- frame-range sharding (native: shard_abi.hip) -------------------------
     def run_sharded(self, comm, frames, n_total: int, series_local, series_all=None, ref=None,
                     ref_resident: bool = False, stream=None) -> None:
@@ -926,7 +1011,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "ChangeMask", "mask_row_bytes", "grid_cell",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "mask_row_bytes", "grid_cell",
     "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",

@@ -222,6 +222,7 @@ void dips_destroy(dips_handle* h) {
         h->pieces.release();
         h->up_pieces.release();
         h->probe_out.release();
+        h->times_parts.release();
         h->io_out.release();
         h->raw.release();
         h->filtered.release();

@@ -233,6 +233,63 @@ struct MaskGenericArgs {
     GridRect roi;
 };
 
+// series_times_kernel (series_times.hip): the change times per pixel of a
+// region -- first, last, longest run, current run, four u32 planes of roi.w *
+// roi.h.  Tiles as series_pixels_kernel's; a wave keeps its tile and walks a
+// part of the frames with the state of its pixels in registers.
+#ifndef DIPS_UNROLL_TIMES
+#define DIPS_UNROLL_TIMES 2
+#endif
+constexpr int kUnrollTimes = DIPS_UNROLL_TIMES;  // vecs per lane: 512 px / wave / frame
+struct TimesArgs {
+    const uint8_t* frames;   // n_frames * frame_bytes, contiguous
+    const uint8_t* ref0;     // overall: reference; per-frame: predecessor of frame 0
+    uint32_t* out;           // one part: the four planes; several: parts x five summary planes (scratch)
+    uint32_t frame_bytes;
+    uint32_t width;          // frame width in pixels (the row pitch)
+    uint32_t n_frames;
+    uint32_t n_tiles;
+    uint32_t n_waves;
+    uint32_t part_frames;    // frames per part (>= 1; one part: >= n_frames)
+    uint32_t t0;             // global index of frames[0]; t0 + n_frames <= 0xFFFFFFFF
+    uint32_t accumulate;     // one part only: fold onto the state `out` holds
+    float thr;               // series_threshold(C, tau, 0)
+    GridRect roi;
+};
+
+// times_combine_kernel: one thread per pixel folds the parts' summaries
+// (parts[(part * 5 + k) * npx + pixel]; k: first, last, run_max, leading,
+// trailing) in order onto the initial or accumulated state in `times`.
+struct TimesCombineArgs {
+    const uint32_t* parts;
+    uint32_t* times;
+    uint32_t frame_bytes;
+    uint32_t width;
+    uint32_t channels;       // 3 or 4: with frame_bytes and width the test for the vecs the fast kernel leaves out
+    uint32_t n_frames;
+    uint32_t part_frames;
+    uint32_t accumulate;
+    GridRect roi;
+};
+
+// times_generic_kernel: one thread per pixel of rect (inside the region)
+// walks the frames; the pixel's four values in `times` written or updated.
+struct TimesGenericArgs {
+    const uint8_t* frames;
+    const uint8_t* ref0;
+    uint32_t* times;
+    uint64_t frame_bytes;
+    uint32_t width;
+    uint32_t n_frames;
+    uint32_t mode;
+    uint32_t chroma;
+    float tau;
+    uint32_t t0;
+    uint32_t accumulate;
+    GridRect roi;
+    GridRect rect;
+};
+
 struct SynthArgs {
     uint8_t* dst;
     uint64_t total_bytes;
@@ -425,6 +482,14 @@ const void* series_mask_kernel_ptr(int channels, int chroma, bool per_frame);
 hipError_t launch_series_mask(const MaskArgs& a, int channels, int chroma, bool per_frame, uint32_t blocks,
                               hipStream_t s);
 hipError_t launch_mask_generic(const MaskGenericArgs& a, int channels, hipStream_t s);
+// the change times per pixel (series_times.hip): RGB8 / RGBA8 fast kernel in
+// its one-part and its several-parts form, the fold of the parts' summaries
+// and the any-format generic kernel
+const void* series_times_kernel_ptr(int channels, int chroma, bool per_frame, bool parts);
+hipError_t launch_series_times(const TimesArgs& a, int channels, int chroma, bool per_frame, bool parts,
+                               uint32_t blocks, hipStream_t s);
+hipError_t launch_times_combine(const TimesCombineArgs& a, hipStream_t s);
+hipError_t launch_times_generic(const TimesGenericArgs& a, int channels, hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 hipError_t launch_read_ceiling(const uint8_t* p, uint64_t bytes, uint32_t* out, hipStream_t s);
 // read-only walk in the RGB8 / RGBA8 series kernel's shape (vec_bytes 12 / 16, U = kUnrollV2Rgb / kUnrollV2)

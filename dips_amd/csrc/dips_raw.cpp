@@ -32,6 +32,12 @@
 //            row_bytes bytes (one bit per pixel, LSB first, rows padded to
 //            32 bits), stdout one line with the region, the frames, the row
 //            bytes and the number of set bits
+//            [--pixel-times FILE [--roi x,y,w,h]] -> the change times per pixel
+//            of the region with dips_diff_pixel_times: FILE gets the four
+//            planes first, last, run_max, run_cur of roi_h x roi_w
+//            little-endian u32 each, stdout one line with the region, the
+//            frames, the pixels that never changed, the smallest first, the
+//            largest last (-1 when no pixel changed) and the largest run_max
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -96,7 +102,7 @@ int usage() {
                  "                [--ranks N [--transport loopback|rccl]]\n"
                  "       dips_raw series IN.raw W H rgb8|rgba8|gray8 [--mode overall|per-frame] [--tau T]\n"
                  "                [--chunk N] [--grid RxC [--roi x,y,w,h]] [--pixel-sums FILE [--roi x,y,w,h]]\n"
-                 "                [--mask FILE [--roi x,y,w,h]]\n"
+                 "                [--mask FILE [--roi x,y,w,h]] [--pixel-times FILE [--roi x,y,w,h]]\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -393,6 +399,7 @@ int run_series(int argc, char** argv) {
     bool has_roi = false;
     const char* pix_path = nullptr;
     const char* mask_path = nullptr;
+    const char* times_path = nullptr;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -416,6 +423,8 @@ int run_series(int argc, char** argv) {
             pix_path = argv[++i];
         } else if (a == "--mask" && has) {
             mask_path = argv[++i];
+        } else if (a == "--pixel-times" && has) {
+            times_path = argv[++i];
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -423,8 +432,9 @@ int run_series(int argc, char** argv) {
             return usage();
         }
     }
-    if (has_roi && rows == 0 && !pix_path && !mask_path) return usage();  // --roi belongs to --grid, --pixel-sums or --mask
-    if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) > 1) return usage();
+    // --roi belongs to --grid, --pixel-sums, --mask or --pixel-times
+    if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path) return usage();
+    if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) > 1) return usage();
     Mapped in;
     if (!in.open(argv[2])) {
         std::fprintf(stderr, "dips_raw: cannot map %s\n", argv[2]);
@@ -515,6 +525,44 @@ int run_series(int argc, char** argv) {
         for (const uint8_t b : mask) set += (unsigned long long)__builtin_popcount(b);
         std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu\n", has_roi ? roi[0] : 0u,
                     has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
+        return 0;
+    }
+    if (times_path) {
+        const uint32_t rw = has_roi ? roi[2] : w, rh = has_roi ? roi[3] : h;
+        // a region the library will refuse gets one value: nothing is written to it
+        uint32_t rect[4];
+        const bool sane = dips_grid_cell(w, h, has_roi ? roi : nullptr, 1u, 1u, 0u, 0u, rect) == DIPS_OK &&
+                          (uint64_t)rw * rh < (1ull << 30);
+        const size_t npx = sane ? (size_t)rw * rh : 0u;
+        std::vector<uint32_t> times(sane ? DIPS_TIMES_PLANES * npx : 1u);
+        st = dips_diff_pixel_times(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, 0u, 0u, times.data());
+        if (st != DIPS_OK) {
+            const int rc = lib_error(hd, "dips_diff_pixel_times", st);
+            dips_destroy(hd);
+            return rc;
+        }
+        dips_destroy(hd);
+        // four planes of roi_h x roi_w little-endian u32 (the host's own order on every target)
+        std::FILE* f = std::fopen(times_path, "wb");
+        if (!f || std::fwrite(times.data(), sizeof(uint32_t), times.size(), f) != times.size() || std::fclose(f) != 0) {
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", times_path);
+            return 1;
+        }
+        unsigned long long never = 0;
+        long long min_first = -1, max_last = -1;
+        uint32_t max_run = 0;
+        for (size_t i = 0; i < npx; ++i) {
+            const uint32_t fi = times[DIPS_TIMES_FIRST * npx + i], la = times[DIPS_TIMES_LAST * npx + i];
+            max_run = std::max(max_run, times[DIPS_TIMES_RUN_MAX * npx + i]);
+            if (fi == DIPS_TIME_NONE) {
+                never += 1;
+                continue;
+            }
+            min_first = min_first < 0 ? (long long)fi : std::min(min_first, (long long)fi);
+            max_last = std::max(max_last, (long long)la);
+        }
+        std::printf("pixel-times roi=%u,%u,%u,%u frames=%u never=%llu min_first=%lld max_last=%lld max_run=%u\n",
+                    has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, never, min_first, max_last, max_run);
         return 0;
     }
     std::vector<dips_series_entry> series(n);

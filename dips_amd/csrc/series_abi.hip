@@ -832,6 +832,164 @@ dips_status run_mask_device(dips_handle* h, uint32_t width, uint32_t height, con
     return DIPS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The change times per pixel (dips_diff_pixel_times; kernels in
+// series_times.hip)
+// ---------------------------------------------------------------------------
+
+struct TimesGeom {
+    bool ok = false;
+    uint32_t part_frames = 0, parts = 0;
+    uint64_t n_tiles = 0, n_waves = 0, blocks = 0;
+};
+
+// Geometry of the fast change-times kernel: pix_geometry's -- a persistent
+// grid of occupancy x CUs waves over items (frame part, tile), one part
+// unless the tiles fill less than 98 % of the wave slots, then enough parts
+// of >= 16 frames to give every slot an item -- without a cap on the frames
+// of a part (the state is u32 indices and run lengths, nothing overflows),
+// and with the parts limited to what keeps their summaries (20 bytes per
+// pixel and part) within kTimesPartsBytes.  DIPS_PIXEL_PART_FRAMES pins the
+// part length as it does there.  Refused (the generic kernel runs): frames of
+// 2^31 bytes or more, 2^28 frames.
+constexpr uint64_t kTimesPartsBytes = 1ull << 30;
+
+TimesGeom times_geometry(dips_handle* h, uint32_t width, uint32_t height, uint32_t n_frames, int C, bool pf,
+                         const dips::GridSpec& g) {
+    TimesGeom q;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    if (fb >= (1ull << 31) || n_frames == 0 || n_frames >= (1u << 28)) return q;
+    const uint64_t vpt = 64u * (uint64_t)dips::kUnrollTimes;  // vecs per tile
+    const uint64_t n_tiles = ((((uint64_t)g.w + 3) / 4) * g.h + vpt - 1) / vpt;
+    if (n_tiles == 0 || n_tiles >= (1ull << 31)) return q;
+    const uint64_t sum_bytes = 20u * (uint64_t)g.w * g.h;  // one part's summaries
+    const uint64_t max_parts = std::max<uint64_t>(1, kTimesPartsBytes / sum_bytes);
+    // the slots of the several-parts form (its fifth register per pixel may
+    // cost it occupancy): that is the form the parts would run
+    const void* kp = dips::series_times_kernel_ptr(C, (int)h->p.chroma_filter, pf, true);
+    if (!kp) return q;
+    const uint64_t res_p = waves_per_simd((uint64_t)occupancy_blocks(h, kp), true) * (uint64_t)h->cu_count * 4u;
+    if (res_p == 0) return q;
+    const uint64_t want = n_tiles * 100u >= res_p * 98u ? 1u : (res_p + n_tiles - 1) / n_tiles;
+    const uint64_t parts = std::max<uint64_t>(1, std::min<uint64_t>(std::min(want, max_parts), n_frames / 16u));
+    q.part_frames = (uint32_t)((n_frames + parts - 1) / parts);
+    if (const char* pin = std::getenv("DIPS_PIXEL_PART_FRAMES")) {
+        const unsigned long L = std::strtoul(pin, nullptr, 10);
+        if (L >= 1 && ((uint64_t)n_frames + L - 1) / L <= max_parts)
+            q.part_frames = (uint32_t)std::min<uint64_t>(L, n_frames);
+    }
+    q.parts = (uint32_t)((n_frames + q.part_frames - 1) / q.part_frames);
+    const void* k = dips::series_times_kernel_ptr(C, (int)h->p.chroma_filter, pf, q.parts > 1);
+    if (!k) return q;
+    const uint64_t resident = waves_per_simd((uint64_t)occupancy_blocks(h, k), true) * (uint64_t)h->cu_count * 4u;
+    if (resident == 0) return q;
+    q.n_tiles = n_tiles;
+    q.n_waves = std::min((uint64_t)q.parts * n_tiles, resident);
+    q.blocks = (q.n_waves + 3) / 4;
+    q.ok = q.blocks < (1ull << 31);
+    return q;
+}
+
+// Run the change times on device pointers, asynchronously on `s`.
+dips_status run_times_device(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames, uint32_t n_frames,
+                             const uint8_t* ref0, const dips::GridSpec& g, uint32_t t0, bool accumulate,
+                             uint32_t* times, hipStream_t s) {
+    const int C = (int)h->p.format;
+    const bool pf = h->p.mode == DIPS_MODE_PER_FRAME;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    const dips::GridRect roi{g.x, g.y, g.w, g.h};
+    TimesGeom q;
+    // GRAY8 has no fast form; DIPS_FLAG_CROSSCHECK asks for the plain kernel
+    if (C != 1 && !(h->p.flags & DIPS_FLAG_FORCE_GENERIC) && !h->crosscheck())
+        q = times_geometry(h, width, height, n_frames, C, pf, g);
+    auto launch_generic = [&](const dips::GridRect& rect) -> dips_status {
+        dips::TimesGenericArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.times = times;
+        a.frame_bytes = fb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.mode = h->p.mode;
+        a.chroma = C == 1 ? 0u : h->p.chroma_filter;
+        a.tau = h->p.tau;
+        a.t0 = t0;
+        a.accumulate = accumulate ? 1u : 0u;
+        a.roi = roi;
+        a.rect = rect;
+        DIPS_HIP(h, dips::launch_times_generic(a, C, s));
+        return DIPS_OK;
+    };
+    // the summaries' buffer before the timed span (growing it synchronises)
+    if (q.ok && q.parts > 1) DIPS_HIP(h, h->times_parts.ensure((size_t)q.parts * 20u * (size_t)g.w * g.h));
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    if (q.ok) {
+        const bool mp = q.parts > 1;
+        dips::TimesArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.out = mp ? h->times_parts.as<uint32_t>() : times;
+        a.frame_bytes = (uint32_t)fb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.n_tiles = (uint32_t)q.n_tiles;
+        a.n_waves = (uint32_t)q.n_waves;
+        a.part_frames = q.part_frames;
+        a.t0 = t0;
+        a.accumulate = !mp && accumulate ? 1u : 0u;
+        a.thr = dips::series_threshold(C, h->p.tau, 0);
+        a.roi = roi;
+        DIPS_HIP(h, dips::launch_series_times(a, C, (int)h->p.chroma_filter, pf, mp, (uint32_t)q.blocks, s));
+        if (mp) {
+            // the parts in order onto the initial or accumulated state: a
+            // later launch, so every summary is written before it is read
+            dips::TimesCombineArgs c{};
+            c.parts = h->times_parts.as<uint32_t>();
+            c.times = times;
+            c.frame_bytes = (uint32_t)fb;
+            c.width = width;
+            c.channels = (uint32_t)C;
+            c.n_frames = n_frames;
+            c.part_frames = q.part_frames;
+            c.accumulate = accumulate ? 1u : 0u;
+            c.roi = roi;
+            DIPS_HIP(h, dips::launch_times_combine(c, s));
+        }
+        // the vecs the fast kernel leaves out (series_times.hip): those that
+        // would read past the frame's end (run_pixels_device's test): the
+        // partial last vec of the region's last rows, one row for frames 3 or
+        // more pixels wide, up to 4 for narrower ones.  Neither the fast
+        // kernel nor the combine touches their <= 3 pixels each
+        if (g.w % 4u != 0u) {
+            const uint32_t x0 = g.x + ((g.w - 1u) & ~3u);  // the last vec of a region row
+            const uint64_t npx = (uint64_t)width * height;
+            for (uint32_t r = g.h; r-- > 0 && g.h - r <= 4u;) {
+                if ((uint64_t)(g.y + r) * width + x0 + 4u <= npx) break;  // it and every earlier row fit
+                dips_status st = launch_generic(dips::GridRect{x0, g.y + r, g.x + g.w - x0, 1u});
+                if (st != DIPS_OK) return st;
+            }
+        }
+    } else {
+        dips_status st = launch_generic(roi);
+        if (st != DIPS_OK) return st;
+    }
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    return DIPS_OK;
+}
+
 // One timed launch of a read-only leg on the handle's stream: *ms = its
 // hipEvent duration (synchronous).
 template <typename Launch>
@@ -1070,6 +1228,67 @@ dips_status dips_diff_change_mask(dips_handle* h, uint32_t width, uint32_t heigh
                              h->stage_map.as<uint8_t>(), h->stream);
         if (st != DIPS_OK) return st;
         DIPS_HIP(h, hipMemcpyAsync(mask, h->stage_map.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_diff_pixel_times(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames,
+                                  uint32_t n_frames, const uint8_t* ref, const uint32_t* roi, uint32_t t0,
+                                  uint32_t accumulate, uint32_t* times) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (!times || (!frames && n_frames > 0)) return fail(h, DIPS_ERR_INVALID, "diff_pixel_times: null argument");
+        dips::GridSpec g{};
+        if (const char* why = grid_spec(width, height, roi, 1u, 1u, &g))
+            return fail(h, DIPS_ERR_INVALID, std::string("diff_pixel_times: ") + why);
+        const uint64_t n_px = (uint64_t)g.w * g.h;
+        if (n_px >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "diff_pixel_times: the region must stay below 2^30 pixels");
+        if ((uint64_t)t0 + n_frames > 0xFFFFFFFFull)
+            return fail(h, DIPS_ERR_INVALID,
+                        "diff_pixel_times: t0 + n_frames must stay below 2^32 (index 0xFFFFFFFF is DIPS_TIME_NONE)");
+        const bool dev = (h->p.flags & DIPS_FLAG_DEVICE_PTRS) != 0;
+        if (dev && ((uintptr_t)times & 3u) != 0)
+            return fail(h, DIPS_ERR_INVALID, "diff_pixel_times: the device times must be 4-byte aligned");
+        const size_t plane_bytes = sizeof(uint32_t) * (size_t)n_px;
+        const size_t out_bytes = DIPS_TIMES_PLANES * plane_bytes;
+        if (n_frames == 0) {
+            // nothing to fold: an overwriting call leaves the initial state
+            if (accumulate != 0u) return DIPS_OK;
+            uint8_t* b = reinterpret_cast<uint8_t*>(times);
+            if (dev) {
+                DIPS_HIP(h, hipMemsetAsync(b, 0xFF, 2u * plane_bytes, h->stream));
+                DIPS_HIP(h, hipMemsetAsync(b + 2u * plane_bytes, 0, 2u * plane_bytes, h->stream));
+            } else {
+                std::memset(b, 0xFF, 2u * plane_bytes);
+                std::memset(b + 2u * plane_bytes, 0, 2u * plane_bytes);
+            }
+            return DIPS_OK;
+        }
+        const int C = (int)h->p.format;
+        const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+        if (dev)
+            return run_times_device(h, width, height, frames, n_frames, ref ? ref : frames, g, t0, accumulate != 0u,
+                                    times, h->stream);
+        // host pointers: stage through HBM (synchronous call)
+        const size_t total = (size_t)fb * n_frames;
+        DIPS_HIP(h, h->stage_frames.ensure(total));
+        DIPS_HIP(h, h->stage_series.ensure(out_bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, frames, total, hipMemcpyHostToDevice, h->stream));
+        if (accumulate != 0u)
+            DIPS_HIP(h, hipMemcpyAsync(h->stage_series.p, times, out_bytes, hipMemcpyHostToDevice, h->stream));
+        const uint8_t* ref_dev = h->stage_frames.as<uint8_t>();
+        if (ref) {
+            DIPS_HIP(h, h->stage_ref.ensure(fb));
+            DIPS_HIP(h, hipMemcpyAsync(h->stage_ref.p, ref, fb, hipMemcpyHostToDevice, h->stream));
+            ref_dev = h->stage_ref.as<uint8_t>();
+        }
+        st = run_times_device(h, width, height, h->stage_frames.as<uint8_t>(), n_frames, ref_dev, g, t0,
+                              accumulate != 0u, h->stage_series.as<uint32_t>(), h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(times, h->stage_series.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

@@ -351,6 +351,49 @@ dips_status dips_diff_change_mask(dips_handle *h, uint32_t width, uint32_t heigh
                                   const uint8_t *frames, uint32_t n_frames, const uint8_t *ref,
                                   const uint32_t *roi, uint8_t *mask);
 
+/* The change times per pixel of a region of interest: when each pixel first
+ * and last changed and for how long it changed without a break.  With
+ * bit(t, j, i) exactly dips_diff_change_mask's bit of frame t and region pixel
+ * (i, j) (strict compare; 'per-frame' mode with ref == NULL: frame 0 all
+ * zero) and g = t0 + t the global index of frames[t], the state of a pixel is
+ * four u32, initially {NONE, NONE, 0, 0}, and the fold of one frame is
+ *   bit = 1: first = (first == NONE ? g : first), last = g, run_cur += 1,
+ *            run_max = max(run_max, run_cur)
+ *   bit = 0: run_cur = 0
+ * so after frames g = t0 .. t0 + n_frames - 1 in order: first / last the
+ * smallest / largest g with bit 1 (DIPS_TIME_NONE if none yet: the arrival
+ * map and the motion-history image), run_max the longest run of consecutive
+ * frames with bit 1 (dwell), run_cur the run that ends at the newest frame (0
+ * if its bit is 0; carried so that a run across two calls is counted whole).
+ * Layout of times: four planes of w * h u32, times[k*w*h + j*w + i] with k =
+ * DIPS_TIMES_FIRST, _LAST, _RUN_MAX, _RUN_CUR; each plane is an image.
+ * accumulate == 0: the call starts from the initial state and overwrites
+ * times (with n_frames == 0 it writes the initial state); accumulate != 0:
+ * the batch is folded onto the state times holds (nothing is written when
+ * n_frames == 0); the caller promises that the batch follows the frames
+ * folded before without a gap -- a clip longer than memory goes chunk by
+ * chunk with t0 = the frames folded so far and the previous chunk's last
+ * frame as ref in 'per-frame' mode, the same reference in 'overall' mode.
+ * Mode, format, tau, chroma_filter, ref and DIPS_FLAG_DEVICE_PTRS as in
+ * dips_diff_pixel_sums (device pointers: asynchronous on the handle's stream,
+ * times 4-byte aligned; host pointers: staged through HBM, synchronous, the
+ * state uploaded first when accumulating; roi is always a host pointer, read
+ * before the call returns).  DIPS_ERR_INVALID for null frames with n_frames
+ * > 0, null times, a device times that is not 4-byte aligned, the roi errors
+ * of dips_grid_cell (at rows = cols = 1), a region of 2^30 pixels or more and
+ * t0 + n_frames > 0xFFFFFFFF (index 0xFFFFFFFF is DIPS_TIME_NONE); times is
+ * then untouched. */
+#define DIPS_TIME_NONE 0xFFFFFFFFu
+#define DIPS_TIMES_FIRST 0u
+#define DIPS_TIMES_LAST 1u
+#define DIPS_TIMES_RUN_MAX 2u
+#define DIPS_TIMES_RUN_CUR 3u
+#define DIPS_TIMES_PLANES 4u
+dips_status dips_diff_pixel_times(dips_handle *h, uint32_t width, uint32_t height,
+                                  const uint8_t *frames, uint32_t n_frames, const uint8_t *ref,
+                                  const uint32_t *roi, uint32_t t0, uint32_t accumulate,
+                                  uint32_t *times);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,
