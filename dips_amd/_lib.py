@@ -42,6 +42,8 @@ MODE_OVERALL = 0
 MODE_PER_FRAME = 1
 
 TIME_NONE = 0xFFFFFFFF  # DIPS_TIME_NONE
+BOX_WORDS = 8  # DIPS_BOX_WORDS; the fields in the order of DIPS_BOX_X0 .. DIPS_BOX_CY256
+BOX_FIELDS = ("x0", "y0", "x1", "y1", "area", "anchor", "cx256", "cy256")
 
 COMM_ID_BYTES = 128
 COMM_RCCL = 1
@@ -185,6 +187,7 @@ def load() -> ctypes.CDLL:
             "dips_mask_row_bytes": ([u32], u32),
             "dips_diff_change_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), _u8p], st),
             "dips_diff_pixel_times": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, _vp], st),
+            "dips_mask_components": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _vp, _vp, _vp], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),
             "dips_diff_series_streamed": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, u32], st),
             "dips_synth_frames": ([_vp, u32, u32, u64, u64, u32, _u8p], st),

@@ -529,6 +529,58 @@ class PixelTimes:
         return cls(a[0].copy(), a[1].copy(), a[2].copy(), a[3].copy())
 
 
+@dataclass
+class ChangeBoxes:
+    """The connected components of a change mask (dips_mask_components):
+    `counts` uint32 [n], the kept components per frame (not capped by K);
+    `boxes` uint32 [n, K, 8], record k of frame t = its k-th kept component
+    by ascending anchor (FIELDS: x0, y0, x1, y1, area, anchor, cx256, cy256;
+    the box is [x0, x1) x [y0, y1), the centroid in 1/256 pixel), zeros past
+    min(counts[t], K); `labels` uint32 [n, h, w] (0: clear or dropped, else
+    1 + the record's index) or None."""
+    counts: np.ndarray
+    boxes: np.ndarray
+    labels: Optional[np.ndarray] = None
+
+    FIELDS = _lib.BOX_FIELDS
+
+    def frame(self, t: int) -> np.ndarray:
+        """uint32 [m, 8]: the m = min(counts[t], K) valid records of frame t."""
+        return self.boxes[t, :min(int(self.counts[t]), self.boxes.shape[1])]
+
+    @property
+    def truncated(self) -> np.ndarray:
+        """bool [n]: frames with more kept components than records."""
+        return self.counts > self.boxes.shape[1]
+
+    def as_arrays(self) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        return self.counts, self.boxes, self.labels
+
+    @classmethod
+    def from_arrays(cls, counts, boxes, labels=None) -> "ChangeBoxes":
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        boxes = np.ascontiguousarray(boxes, dtype=np.uint32)
+        if counts.ndim != 1 or boxes.ndim != 3 or boxes.shape[0] != counts.shape[0] or boxes.shape[2] != _lib.BOX_WORDS:
+            raise ValueError("counts must be [n] and boxes [n, K, 8]")
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.uint32)
+            if labels.ndim != 3 or labels.shape[0] != counts.shape[0]:
+                raise ValueError("labels must be [n, h, w]")
+        return cls(counts, boxes, labels)
+
+
+def _components_args(connectivity, min_area, max_boxes, chunk_frames, n: int) -> Tuple[int, int, int, int]:
+    """The scalar arguments of dips_mask_components, checked."""
+    if int(connectivity) not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    for name, v in (("min_area", min_area), ("max_boxes", max_boxes), ("chunk_frames", chunk_frames)):
+        if int(v) < 0 or int(v) > 0xFFFFFFFF:
+            raise ValueError(f"{name} must be a non-negative 32-bit integer")
+    if n * int(max_boxes) * _lib.BOX_WORDS >= 1 << 32:
+        raise ValueError("n_frames * max_boxes * 8 must stay below 2^32")
+    return int(connectivity), int(min_area), int(max_boxes), int(chunk_frames)
+
+
 def _roi_arg(roi):
     """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
     if roi is None:
@@ -805,6 +857,100 @@ class DiffSeriesOperator:
                 ref.data_ptr() if ref is not None else None, _roi_arg(roi),
                 mask_out.data_ptr() if mask_out.numel() else None))
 
+    # -- the connected components of a change mask (dips_mask_components) ----
+    def mask_components(self, mask: ChangeMask, connectivity: int = 8, min_area: int = 1, max_boxes: int = 64,
+                        labels: bool = False, chunk_frames: int = 0) -> ChangeBoxes:
+        """The components of every frame of `mask` (what change_mask
+        returns) under 4- or 8-connectivity: those of at least min_area
+        pixels, counted per frame, the first max_boxes of a frame by
+        ascending anchor as records, and (labels=True) the label image.  A
+        mask that lives on the device goes through
+        run_mask_components_device."""
+        if not isinstance(mask, ChangeMask):
+            raise ValueError("mask must be a ChangeMask")
+        bits = np.ascontiguousarray(mask.bits, dtype=np.uint8)
+        rw = int(mask.width)
+        if bits.ndim != 3 or rw < 0 or bits.shape[2] != 4 * ((rw + 31) // 32):
+            raise ValueError("mask.bits must be [n, h, 4 * ceil(width / 32)] bytes")
+        n, rh = int(bits.shape[0]), int(bits.shape[1])
+        conn, area, k, chunk = _components_args(connectivity, min_area, max_boxes, chunk_frames, n)
+        counts = np.zeros(n, dtype=np.uint32)
+        boxes = np.zeros((n, k, _lib.BOX_WORDS), dtype=np.uint32)
+        lab = np.zeros((n, rh, rw), dtype=np.uint32) if labels else None
+        self._host.check(self._host._lib.dips_mask_components(
+            self._host.ptr, bits.ctypes.data if bits.size else None, n, rw, rh, conn, area, k, chunk,
+            counts.ctypes.data if n else None, boxes.ctypes.data if boxes.size else None,
+            lab.ctypes.data if lab is not None and lab.size else None))
+        return ChangeBoxes(counts, boxes, lab)
+
+    def run_mask_components_device(self, mask, width: int, counts_out, boxes_out=None, labels_out=None,
+                                   connectivity: int = 8, min_area: int = 1, chunk_frames: int = 0,
+                                   stream=None) -> None:
+        """Asynchronous: mask a uint8 device tensor [N, h, row_bytes] as
+        run_change_mask_device writes it for a region `width` pixels wide;
+        counts_out [N], boxes_out [N, K, 8] (None: counts only) and
+        labels_out [N, h, width] (None: not produced) 4-byte device tensors,
+        all 4-byte aligned; every element of them is written."""
+        import torch
+        rw = int(width)
+        if mask.dim() != 3 or rw < 0 or mask.shape[2] != 4 * ((rw + 31) // 32) or mask.dtype != torch.uint8:
+            raise ValueError("mask must be a uint8 tensor of shape [N, h, 4 * ceil(width / 32)]")
+        n, rh = int(mask.shape[0]), int(mask.shape[1])
+        k = 0
+        if boxes_out is not None:
+            if boxes_out.dim() != 3 or boxes_out.shape[0] != n or boxes_out.shape[2] != _lib.BOX_WORDS:
+                raise ValueError("boxes_out must be a 4-byte tensor of shape [N, K, 8]")
+            k = int(boxes_out.shape[1])
+        conn, area, k, chunk = _components_args(connectivity, min_area, k, chunk_frames, n)
+        if tuple(counts_out.shape) != (n,):
+            raise ValueError("counts_out must be a 4-byte tensor of shape [N]")
+        if labels_out is not None and tuple(labels_out.shape) != (n, rh, rw):
+            raise ValueError("labels_out must be a 4-byte tensor of shape [N, h, width]")
+        for t in (counts_out, boxes_out, labels_out):
+            if t is not None and t.element_size() != 4:
+                raise ValueError("counts_out, boxes_out and labels_out must be 4-byte tensors")
+        for t in (mask, counts_out, boxes_out, labels_out):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_components(
+                self._dev.ptr, mask.data_ptr() if mask.numel() else None, n, rw, rh, conn, area, k, chunk,
+                counts_out.data_ptr() if n else None,
+                boxes_out.data_ptr() if boxes_out is not None and boxes_out.numel() else None,
+                labels_out.data_ptr() if labels_out is not None and labels_out.numel() else None))
+
+    def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
+                     max_boxes: int = 64, labels: bool = False) -> ChangeBoxes:
+        """change_mask, then mask_components, with the mask kept on the
+        device between the two: the moving objects of every frame.  frames /
+        ref: numpy arrays (uploaded once) or uint8 device tensors."""
+        import torch
+        dev = torch.device("cuda", self._dev.device)
+
+        def on_device(a):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            return torch.from_numpy(_as_u8(a)).to(dev)
+
+        frames, ref = on_device(frames), on_device(ref)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        _, _, k, _ = _components_args(connectivity, min_area, max_boxes, 0, n)
+        if ref is not None:
+            ref = ref.reshape(-1)
+        mask = torch.empty((n, rh, 4 * ((rw + 31) // 32)), dtype=torch.uint8, device=dev)
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
+        lab = torch.empty((n, rh, rw), dtype=torch.int32, device=dev) if labels else None
+        self.run_change_mask_device(frames, mask, roi=roi, ref=ref)
+        self.run_mask_components_device(mask, rw, counts, boxes, lab, connectivity=connectivity, min_area=min_area)
+
+        def to_u32(t):
+            return t.cpu().numpy().view(np.uint32)  # the copy waits for the stream
+
+        return ChangeBoxes(to_u32(counts), to_u32(boxes), to_u32(lab) if lab is not None else None)
+
     # -- the change times per pixel (dips_diff_pixel_times) --------------------
     def pixel_times(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None, t0: int = 0,
                     into: Optional[PixelTimes] = None) -> PixelTimes:
@@ -1011,7 +1157,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "mask_row_bytes", "grid_cell",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "mask_row_bytes", "grid_cell",
     "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",

@@ -223,6 +223,7 @@ void dips_destroy(dips_handle* h) {
         h->up_pieces.release();
         h->probe_out.release();
         h->times_parts.release();
+        h->cc_scratch.release();
         h->io_out.release();
         h->raw.release();
         h->filtered.release();

@@ -42,6 +42,7 @@ struct dips_handle {
     dips_host::DevBuf partials, stage_frames, stage_ref, stage_series, stage_map;
     dips_host::DevBuf probe_out;  // sink of the read-ceiling kernels
     dips_host::DevBuf times_parts;  // per-part summaries of dips_diff_pixel_times (series_times.hip)
+    dips_host::DevBuf cc_scratch;   // union-find and statistics of dips_mask_components (mask_components.hip)
     std::map<const void*, int> occupancy;
 
     // streamed feed

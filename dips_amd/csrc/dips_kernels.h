@@ -290,6 +290,35 @@ struct TimesGenericArgs {
     GridRect rect;
 };
 
+// The connected components of a chunk of change-mask frames
+// (mask_components.hip).  Scratch per frame: parent, one u32 per pixel, and
+// the statistics of the word-local runs, one slot per two pixels of a row.
+struct ComponentsArgs {
+    const uint32_t* mask;   // the chunk's frames, h * wpr words each
+    uint32_t* parent;       // n_frames * npx
+    uint64_t* sum_i;        // n_frames * nslots each, from here on
+    uint64_t* sum_j;
+    uint32_t* area;         // after cc_select_kernel: the label
+    uint32_t* min_x;
+    uint32_t* max_x;
+    uint32_t* max_y;
+    uint32_t* block_count;  // n_frames * bpf: kept roots per block, then their exclusive scan
+    uint32_t* counts;       // the chunk's part of the outputs
+    uint32_t* boxes;        // NULL with max_boxes = 0; cleared by the host
+    uint32_t* labels;       // NULL: not produced
+    uint32_t w, h;
+    uint32_t npx;           // w * h < 2^30
+    uint32_t wpr;           // mask words per row
+    uint32_t hw;            // slots per row, ceil(w / 2)
+    uint32_t nslots;        // hw * h
+    uint32_t wpf;           // mask words per frame
+    uint32_t bpf;           // blocks of 256 words per frame
+    uint32_t n_frames;      // of the chunk
+    uint32_t connectivity;  // 4 or 8
+    uint32_t min_area;
+    uint32_t max_boxes;
+};
+
 struct SynthArgs {
     uint8_t* dst;
     uint64_t total_bytes;
@@ -490,6 +519,9 @@ hipError_t launch_series_times(const TimesArgs& a, int channels, int chroma, boo
                                uint32_t blocks, hipStream_t s);
 hipError_t launch_times_combine(const TimesCombineArgs& a, hipStream_t s);
 hipError_t launch_times_generic(const TimesGenericArgs& a, int channels, hipStream_t s);
+// the connected components of a chunk of mask frames (mask_components.hip):
+// every launch of the chunk, in order, on `s`
+hipError_t launch_mask_components(const ComponentsArgs& a, hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 hipError_t launch_read_ceiling(const uint8_t* p, uint64_t bytes, uint32_t* out, hipStream_t s);
 // read-only walk in the RGB8 / RGBA8 series kernel's shape (vec_bytes 12 / 16, U = kUnrollV2Rgb / kUnrollV2)

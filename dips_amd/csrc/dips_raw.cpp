@@ -38,6 +38,13 @@
 //            little-endian u32 each, stdout one line with the region, the
 //            frames, the pixels that never changed, the smallest first, the
 //            largest last (-1 when no pixel changed) and the largest run_max
+//            [--boxes FILE [--connectivity 4|8] [--min-area A] [--max-boxes K]
+//            [--roi x,y,w,h]] -> the connected components of the region's
+//            change mask with dips_diff_change_mask and dips_mask_components
+//            (defaults 8, 1, 64): FILE gets the CSV frame,k,x0,y0,x1,y1,area,
+//            anchor,cx256,cy256, one row per stored record, and a line
+//            "# frame,count" per frame (count is not capped by K); stdout one
+//            line with the region, the frames, the components and the records
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -103,6 +110,7 @@ int usage() {
                  "       dips_raw series IN.raw W H rgb8|rgba8|gray8 [--mode overall|per-frame] [--tau T]\n"
                  "                [--chunk N] [--grid RxC [--roi x,y,w,h]] [--pixel-sums FILE [--roi x,y,w,h]]\n"
                  "                [--mask FILE [--roi x,y,w,h]] [--pixel-times FILE [--roi x,y,w,h]]\n"
+                 "                [--boxes FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -119,6 +127,15 @@ bool parse_u32(const char* s, uint32_t* v) {
     if (!s[0] || *end || x == 0 || x > 0xFFFFFFFFul) return false;
     *v = (uint32_t)x;
     return true;
+}
+
+// as parse_u32, 0 allowed (--min-area, --max-boxes)
+bool parse_u32_or_zero(const char* s, uint32_t* v) {
+    if (s[0] == '0' && !s[1]) {
+        *v = 0;
+        return true;
+    }
+    return parse_u32(s, v);
 }
 
 // "RxC" -> rows, cols (both >= 1)
@@ -400,6 +417,9 @@ int run_series(int argc, char** argv) {
     const char* pix_path = nullptr;
     const char* mask_path = nullptr;
     const char* times_path = nullptr;
+    const char* boxes_path = nullptr;
+    uint32_t connectivity = 8, min_area = 1, max_boxes = 64;
+    bool has_box_opt = false;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -425,6 +445,12 @@ int run_series(int argc, char** argv) {
             mask_path = argv[++i];
         } else if (a == "--pixel-times" && has) {
             times_path = argv[++i];
+        } else if (a == "--boxes" && has) {
+            boxes_path = argv[++i];
+        } else if ((a == "--connectivity" || a == "--min-area" || a == "--max-boxes") && has) {
+            uint32_t* v = a == "--connectivity" ? &connectivity : a == "--min-area" ? &min_area : &max_boxes;
+            if (!parse_u32_or_zero(argv[++i], v)) return usage();
+            has_box_opt = true;
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -432,9 +458,13 @@ int run_series(int argc, char** argv) {
             return usage();
         }
     }
-    // --roi belongs to --grid, --pixel-sums, --mask or --pixel-times
-    if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path) return usage();
-    if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) > 1) return usage();
+    // --roi belongs to --grid, --pixel-sums, --mask, --pixel-times or --boxes
+    if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path && !boxes_path) return usage();
+    if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) +
+            (boxes_path != nullptr) > 1)
+        return usage();
+    if (has_box_opt && !boxes_path) return usage();
+    if (connectivity != 4u && connectivity != 8u) return usage();
     Mapped in;
     if (!in.open(argv[2])) {
         std::fprintf(stderr, "dips_raw: cannot map %s\n", argv[2]);
@@ -525,6 +555,53 @@ int run_series(int argc, char** argv) {
         for (const uint8_t b : mask) set += (unsigned long long)__builtin_popcount(b);
         std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu\n", has_roi ? roi[0] : 0u,
                     has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
+        return 0;
+    }
+    if (boxes_path) {
+        const uint32_t rw = has_roi ? roi[2] : w, rh = has_roi ? roi[3] : h;
+        // a region or a record count the library will refuse gets one element: nothing is written to it
+        uint32_t rect[4];
+        const bool sane = dips_grid_cell(w, h, has_roi ? roi : nullptr, 1u, 1u, 0u, 0u, rect) == DIPS_OK &&
+                          (uint64_t)rw * rh < (1ull << 30) && rw < (1u << 24) && rh < (1u << 24) &&
+                          (uint64_t)n * max_boxes * DIPS_BOX_WORDS < (1ull << 32);
+        std::vector<uint8_t> mask(sane ? (size_t)n * rh * dips_mask_row_bytes(rw) : 1u);
+        std::vector<uint32_t> counts(sane ? (size_t)n : 1u), recs(sane ? (size_t)n * max_boxes * DIPS_BOX_WORDS : 1u);
+        const char* what = "dips_diff_change_mask";
+        st = dips_diff_change_mask(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, mask.data());
+        if (st == DIPS_OK) {
+            what = "dips_mask_components";
+            st = dips_mask_components(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, counts.data(),
+                                      max_boxes ? recs.data() : nullptr, nullptr);
+        }
+        if (st != DIPS_OK) {
+            const int rc = lib_error(hd, what, st);
+            dips_destroy(hd);
+            return rc;
+        }
+        dips_destroy(hd);
+        std::FILE* f = std::fopen(boxes_path, "w");
+        if (!f) {
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", boxes_path);
+            return 1;
+        }
+        std::fprintf(f, "frame,k,x0,y0,x1,y1,area,anchor,cx256,cy256\n");
+        unsigned long long total = 0, stored = 0;
+        for (uint32_t t = 0; t < n; ++t) {
+            std::fprintf(f, "# %u,%u\n", t, counts[t]);
+            total += counts[t];
+            for (uint32_t k = 0; k < std::min(counts[t], max_boxes); ++k, ++stored) {
+                const uint32_t* r = &recs[((size_t)t * max_boxes + k) * DIPS_BOX_WORDS];
+                std::fprintf(f, "%u,%u,%u,%u,%u,%u,%u,%u,%u,%u\n", t, k, r[DIPS_BOX_X0], r[DIPS_BOX_Y0], r[DIPS_BOX_X1],
+                             r[DIPS_BOX_Y1], r[DIPS_BOX_AREA], r[DIPS_BOX_ANCHOR], r[DIPS_BOX_CX256], r[DIPS_BOX_CY256]);
+            }
+        }
+        if (std::ferror(f) != 0 || std::fclose(f) != 0) {
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", boxes_path);
+            return 1;
+        }
+        std::printf("boxes roi=%u,%u,%u,%u frames=%u connectivity=%u min_area=%u max_boxes=%u components=%llu records=%llu\n",
+                    has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, connectivity, min_area, max_boxes, total,
+                    stored);
         return 0;
     }
     if (times_path) {

@@ -990,6 +990,77 @@ dips_status run_times_device(dips_handle* h, uint32_t width, uint32_t height, co
     return DIPS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The connected components of a mask (dips_mask_components; kernels in
+// mask_components.hip)
+// ---------------------------------------------------------------------------
+
+constexpr size_t kComponentsScratchBytes = (size_t)1 << 30;  // chunk_frames = 0 stays within this
+
+// Label the frames of a device mask, asynchronously on `s`, `chunk` frames
+// per round (0: automatic) in the handle's scratch.
+dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                                  uint32_t connectivity, uint32_t min_area, uint32_t max_boxes, uint32_t chunk,
+                                  uint32_t* counts, uint32_t* boxes, uint32_t* labels, hipStream_t s) {
+    dips::ComponentsArgs a{};
+    a.w = w;
+    a.h = hgt;
+    a.npx = w * hgt;
+    a.wpr = (uint32_t)mask_words_per_row(w);
+    a.hw = (w + 1u) / 2u;
+    a.nslots = a.hw * hgt;
+    a.wpf = a.wpr * hgt;
+    a.bpf = (a.wpf + 255u) / 256u;
+    a.connectivity = connectivity;
+    a.min_area = min_area;
+    a.max_boxes = max_boxes;
+    // per frame: parent, six statistics (two of 8 bytes) per slot, the block sums
+    const size_t per_frame = 4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf;
+    uint64_t frames = chunk ? chunk : std::max<uint64_t>(1u, kComponentsScratchBytes / per_frame);
+    frames = std::min<uint64_t>(frames, n_frames);
+    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
+    const uint32_t F = (uint32_t)frames;
+    // the scratch before the timed span (growing it synchronises)
+    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F));
+    uint8_t* base = h->cc_scratch.as<uint8_t>();
+    a.sum_i = reinterpret_cast<uint64_t*>(base);
+    a.sum_j = a.sum_i + (size_t)F * a.nslots;
+    a.area = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);
+    a.min_x = a.area + (size_t)F * a.nslots;
+    a.max_x = a.min_x + (size_t)F * a.nslots;
+    a.max_y = a.max_x + (size_t)F * a.nslots;
+    a.parent = a.max_y + (size_t)F * a.nslots;
+    a.block_count = a.parent + (size_t)F * a.npx;
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    // the records no component fills are zeros
+    if (max_boxes != 0u)
+        DIPS_HIP(h, hipMemsetAsync(boxes, 0, sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes, s));
+    const size_t frame_words = (size_t)a.wpf;
+    for (uint32_t t = 0; t < n_frames; t += F) {
+        a.n_frames = std::min(F, n_frames - t);
+        a.mask = reinterpret_cast<const uint32_t*>(mask) + (size_t)t * frame_words;
+        a.counts = counts + t;
+        a.boxes = max_boxes != 0u ? boxes + (size_t)t * max_boxes * DIPS_BOX_WORDS : nullptr;
+        a.labels = labels ? labels + (size_t)t * a.npx : nullptr;
+        DIPS_HIP(h, dips::launch_mask_components(a, s));
+    }
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    return DIPS_OK;
+}
+
 // One timed launch of a read-only leg on the handle's stream: *ms = its
 // hipEvent duration (synchronous).
 template <typename Launch>
@@ -1289,6 +1360,56 @@ dips_status dips_diff_pixel_times(dips_handle* h, uint32_t width, uint32_t heigh
                               accumulate != 0u, h->stage_series.as<uint32_t>(), h->stream);
         if (st != DIPS_OK) return st;
         DIPS_HIP(h, hipMemcpyAsync(times, h->stage_series.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_components(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w,
+                                 uint32_t roi_h, uint32_t connectivity, uint32_t min_area, uint32_t max_boxes,
+                                 uint32_t chunk_frames, uint32_t* counts, uint32_t* boxes, uint32_t* labels) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask || !counts || (!boxes && max_boxes != 0u))
+            return fail(h, DIPS_ERR_INVALID, "mask_components: null argument");
+        if (connectivity != 4u && connectivity != 8u)
+            return fail(h, DIPS_ERR_INVALID, "mask_components: connectivity must be 4 or 8");
+        if (roi_w == 0 || roi_h == 0 || roi_w >= (1u << 24) || roi_h >= (1u << 24))
+            return fail(h, DIPS_ERR_INVALID, "mask_components: roi_w and roi_h must be 1 .. 2^24 - 1");
+        const uint64_t n_px = (uint64_t)roi_w * roi_h;
+        if (n_px >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_components: the region must stay below 2^30 pixels");
+        if ((uint64_t)n_frames * max_boxes * DIPS_BOX_WORDS >= (1ull << 32))
+            return fail(h, DIPS_ERR_INVALID, "mask_components: n_frames * max_boxes * 8 must stay below 2^32");
+        if (max_boxes == 0u) boxes = nullptr;
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            if ((((uintptr_t)mask | (uintptr_t)counts | (uintptr_t)boxes | (uintptr_t)labels) & 3u) != 0)
+                return fail(h, DIPS_ERR_INVALID, "mask_components: the device pointers must be 4-byte aligned");
+            return run_components_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
+                                         chunk_frames, counts, boxes, labels, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call); counts and
+        // boxes share one buffer
+        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const size_t counts_bytes = sizeof(uint32_t) * (size_t)n_frames;
+        const size_t boxes_bytes = sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
+        const size_t labels_bytes = labels ? sizeof(uint32_t) * (size_t)n_px * n_frames : 0u;
+        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes));
+        DIPS_HIP(h, h->stage_series.ensure(counts_bytes + boxes_bytes));
+        if (labels) DIPS_HIP(h, h->stage_map.ensure(labels_bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        uint32_t* counts_dev = h->stage_series.as<uint32_t>();
+        uint32_t* boxes_dev = max_boxes != 0u ? counts_dev + n_frames : nullptr;
+        st = run_components_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, connectivity, min_area,
+                                   max_boxes, chunk_frames, counts_dev, boxes_dev,
+                                   labels ? h->stage_map.as<uint32_t>() : nullptr, h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (max_boxes != 0u)
+            DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (labels) DIPS_HIP(h, hipMemcpyAsync(labels, h->stage_map.p, labels_bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

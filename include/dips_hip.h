@@ -394,6 +394,61 @@ dips_status dips_diff_pixel_times(dips_handle *h, uint32_t width, uint32_t heigh
                                   const uint32_t *roi, uint32_t t0, uint32_t accumulate,
                                   uint32_t *times);
 
+/* The connected components of a change mask, frame by frame: the blobs and
+ * bounding boxes the README promises the mask "feeds" (difference ->
+ * threshold -> components -> boxes).  The reference has no counterpart.  A
+ * second stage behind dips_diff_change_mask: it reads the mask, not the
+ * frames, so it serves every pixel format, and the answer is combinatorial,
+ * hence exact.
+ * Input: mask in exactly dips_diff_change_mask's layout -- n_frames frames of
+ * roi_h rows of dips_mask_row_bytes(roi_w) bytes, bit i of a row = bit
+ * (i & 31) of little-endian word i >> 5.  The pad bits of a row's last word
+ * are ignored, whatever they hold.  Frames are independent: nothing connects
+ * the last row of frame t to frame t + 1, or a row's end to the next row.
+ * Components: the set pixels of frame t partitioned under connectivity 4
+ * (edge neighbours) or 8 (edge and corner neighbours).  The anchor of a
+ * component is j*roi_w + i of its first pixel in row-major order; a
+ * component is kept if its area is >= min_area (0 and 1 keep all); the kept
+ * components of a frame are ordered by ascending anchor.
+ * Outputs: counts[t] = the kept components of frame t, not capped by
+ * max_boxes (truncation is visible).  boxes[(t*max_boxes + k)*DIPS_BOX_WORDS
+ * + f] is the k-th kept component for k < min(counts[t], max_boxes); every
+ * other record is zeros and every word of boxes is written.  Fields: X0, Y0
+ * the smallest i, j (region-relative), X1, Y1 the largest i, j plus 1 (the
+ * box is [X0, X1) x [Y0, Y1)), AREA the pixels, ANCHOR as above, CX256 /
+ * CY256 the centroid in 1/256 pixel: (S / area)*256 + ((S % area)*256) / area
+ * with S the exact 64-bit sum of i (of j), both divisions floor.  labels
+ * (NULL: not produced) is labels[(t*roi_h + j)*roi_w + i]: 0 for a clear bit
+ * or a dropped component, else 1 + the component's rank among the frame's
+ * kept ones (not capped by max_boxes: label k + 1 is record k where both
+ * exist).
+ * chunk_frames: frames labelled per round in handle-owned scratch (grown on
+ * demand, freed with the handle); 0 = as many as keep it within 1 GiB, at
+ * least one.  The result does not depend on it; DIPS_ERR_NOMEM if the scratch
+ * cannot be allocated.  The time depends on the bits.
+ * DIPS_FLAG_DEVICE_PTRS: all four pointers are device pointers, 4-byte
+ * aligned, the call asynchronous on the handle's stream; else host pointers
+ * of any alignment, staged through HBM, synchronous.  DIPS_FLAG_TIME_KERNEL:
+ * one entry for all launches of the call.  n_frames == 0: DIPS_OK, nothing
+ * written.  DIPS_ERR_INVALID, outputs untouched: null mask or counts, null
+ * boxes with max_boxes > 0, a misaligned device pointer, connectivity not 4
+ * or 8, roi_w or roi_h of 0 or >= 2^24 (CX256 stays in 32 bits), a region of
+ * 2^30 pixels or more, n_frames*max_boxes*DIPS_BOX_WORDS >= 2^32. */
+#define DIPS_BOX_X0 0u
+#define DIPS_BOX_Y0 1u
+#define DIPS_BOX_X1 2u
+#define DIPS_BOX_Y1 3u
+#define DIPS_BOX_AREA 4u
+#define DIPS_BOX_ANCHOR 5u
+#define DIPS_BOX_CX256 6u
+#define DIPS_BOX_CY256 7u
+#define DIPS_BOX_WORDS 8u
+dips_status dips_mask_components(dips_handle *h, const uint8_t *mask, uint32_t n_frames,
+                                 uint32_t roi_w, uint32_t roi_h,
+                                 uint32_t connectivity, uint32_t min_area, uint32_t max_boxes,
+                                 uint32_t chunk_frames,
+                                 uint32_t *counts, uint32_t *boxes, uint32_t *labels);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,

@@ -188,6 +188,9 @@ extern "C" {
     pub fn dips_diff_pixel_times(h: *mut DipsHandle, width: u32, height: u32, frames: *const u8, n_frames: u32,
                                  reference: *const u8, roi: *const u32, t0: u32, accumulate: u32,
                                  times: *mut u32) -> DipsStatus;
+    pub fn dips_mask_components(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32,
+                                connectivity: u32, min_area: u32, max_boxes: u32, chunk_frames: u32,
+                                counts: *mut u32, boxes: *mut u32, labels: *mut u32) -> DipsStatus;
     pub fn dips_synth_frames(h: *mut DipsHandle, width: u32, height: u32, seed: u64, t0: u64, n_frames: u32,
                              dst: *mut u8) -> DipsStatus;
     pub fn dips_kernel_time(h: *mut DipsHandle, total_ms: *mut f64, launches: *mut u64) -> DipsStatus;
