@@ -524,18 +524,25 @@ dips_status run_grid_device(dips_handle* h, uint32_t width, uint32_t height, con
         a.g = g;
         DIPS_HIP(h, dips::launch_series_grid(a, C, (int)h->p.chroma_filter, pf, isi, (uint32_t)q.blocks, s));
         // the vecs the fast kernel leaves out (series_grid.hip): a partial
-        // last vec in the frame's last row that starts within 3 pixels of the
-        // frame's right edge would read past the frame's end.  Their <= 3
-        // pixels go into their cells by atomics (after the kernel's zeroing);
-        // cell edges decrease with the column, so at most three cells qualify
-        if (g.y + g.h == height) {
+        // last vec of a cell row that starts within 3 pixels of the frame's
+        // end would read past it.  A full vec ends inside its row, so these
+        // lie in the frame's last row, and in frames narrower than 3 pixels
+        // in up to three rows before it (run_pixels_device applies the same
+        // test).  Their <= 3 pixels go into their cells by atomics (after the
+        // kernel's zeroing); cell edges decrease with the column, so at most
+        // three cells of a row qualify
+        const uint64_t npx = (uint64_t)width * height;
+        uint32_t crow = g.rows - 1u;  // the grid row of region row y
+        for (uint32_t y = g.y + g.h; y-- > g.y;) {
+            if (((uint64_t)y + 1u) * width + 3u <= npx) break;  // every vec of this and the earlier rows fits
+            while (dips::grid_cell_rect(g, crow, 0u).y > y) --crow;
             for (uint32_t c = g.cols; c-- > 0;) {
-                const dips::GridRect rc = dips::grid_cell_rect(g, g.rows - 1u, c);
-                if (rc.x + rc.w + 3u <= width) break;  // every vec of this and the earlier columns fits
-                const uint32_t x0 = rc.x + ((rc.w - 1u) & ~3u);  // its last vec
-                if (rc.w % 4u == 0u || x0 + 4u <= width) continue;
-                const dips::GridSpec tail{x0, height - 1u, rc.x + rc.w - x0, 1u, 1u, 1u};
-                dips_status st = launch_generic(tail, (g.rows - 1u) * g.cols + c);
+                const dips::GridRect rc = dips::grid_cell_rect(g, crow, c);
+                if ((uint64_t)y * width + rc.x + rc.w + 3u <= npx) break;  // so does every vec of the earlier columns
+                const uint32_t x0 = rc.x + ((rc.w - 1u) & ~3u);  // the cell row's last vec
+                if (rc.w % 4u == 0u || (uint64_t)y * width + x0 + 4u <= npx) continue;
+                const dips::GridSpec tail{x0, y, rc.x + rc.w - x0, 1u, 1u, 1u};
+                dips_status st = launch_generic(tail, crow * g.cols + c);
                 if (st != DIPS_OK) return st;
             }
         }

@@ -29,12 +29,13 @@
 // the frame loop anyway and the branch doubled the ring's live ranges: 250+
 // VGPRs.)
 //
-// A few vecs are left out: a partial last vec in the frame's last row that
-// starts within 3 pixels of the frame's right edge would read past the
-// frame's end (the corner cell when its width is no multiple of 4; cells
-// narrower than a vec next to it).  Such a slot is invalid here and the host
-// adds its <= 3 pixels with the generic kernel below, as series_abi.hip does
-// for the ragged tail of a whole frame.
+// A few vecs are left out: a partial last vec of a cell row that starts
+// within 3 pixels of the frame's end would read past it (in the frame's last
+// row the corner cell when its width is no multiple of 4 and cells narrower
+// than a vec next to it; in frames narrower than 3 pixels also vecs of up to
+// three rows before the last).  Such a slot is invalid here and the host adds
+// its <= 3 pixels with the generic kernel below, as series_abi.hip does for
+// the ragged tail of a whole frame.
 //
 // Schedule: a persistent grid, items (frame part, tile) dealt part-major with
 // stride n_waves as in series_v2_body, a 4-slot register ring of frames (three
