@@ -48,6 +48,20 @@ class Mode(enum.IntEnum):
     PerFrame = _lib.MODE_PER_FRAME  # against the previous frame (README.md:8-10)
 
 
+class MorphOp(enum.IntEnum):
+    """The operation of dips_mask_morph."""
+    Erode = _lib.MORPH_ERODE
+    Dilate = _lib.MORPH_DILATE
+    Open = _lib.MORPH_OPEN    # erode, then dilate
+    Close = _lib.MORPH_CLOSE  # dilate, then erode
+
+
+class MorphShape(enum.IntEnum):
+    """The structuring element of dips_mask_morph."""
+    Box = _lib.MORPH_BOX          # |dx| <= rx, |dy| <= ry
+    Diamond = _lib.MORPH_DIAMOND  # |dx| + |dy| <= rx (ry == rx)
+
+
 class VideoPathNotSpecifiedError(Exception):
     """dips/src/lib.rs:173-186"""
 
@@ -581,6 +595,35 @@ def _components_args(connectivity, min_area, max_boxes, chunk_frames, n: int) ->
     return int(connectivity), int(min_area), int(max_boxes), int(chunk_frames)
 
 
+def _morph_args(op, shape, rx, ry, w: int, h: int) -> Tuple[int, int, int, int]:
+    """The scalar arguments of dips_mask_morph, checked; ry None means rx."""
+    try:
+        op, shape = int(MorphOp(op)), int(MorphShape(shape))
+    except ValueError:
+        raise ValueError("op must be a MorphOp (0 .. 3) and shape a MorphShape (0 or 1)") from None
+    rx = int(rx)
+    ry = rx if ry is None else int(ry)
+    if not (0 <= rx <= _lib.MORPH_MAX_RADIUS and 0 <= ry <= _lib.MORPH_MAX_RADIUS):
+        raise ValueError(f"rx and ry must be 0 .. {_lib.MORPH_MAX_RADIUS}")
+    if shape == MorphShape.Diamond and ry != rx:
+        raise ValueError("a diamond needs ry == rx")
+    if w <= 0 or h <= 0:
+        raise ValueError("the mask's width and height must not be 0")
+    if w * h >= 1 << 30:
+        raise ValueError("the region must stay below 2^30 pixels")
+    return op, shape, rx, ry
+
+
+def _morph_steps(morph, w: int, h: int) -> List[Tuple[int, int, int, int]]:
+    """change_boxes' morph: a sequence of (op, shape, rx, ry) steps, checked."""
+    steps = []
+    for step in morph:
+        if len(step) != 4:
+            raise ValueError("a morph step must be (op, shape, rx, ry)")
+        steps.append(_morph_args(step[0], step[1], step[2], step[3], w, h))
+    return steps
+
+
 def _roi_arg(roi):
     """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
     if roi is None:
@@ -920,11 +963,63 @@ class DiffSeriesOperator:
                 boxes_out.data_ptr() if boxes_out is not None and boxes_out.numel() else None,
                 labels_out.data_ptr() if labels_out is not None and labels_out.numel() else None))
 
+    # -- the binary morphology of a change mask (dips_mask_morph) -------------
+    def mask_morph(self, mask: ChangeMask, op, rx: int = 1, ry: Optional[int] = None,
+                   shape=MorphShape.Box) -> ChangeMask:
+        """Every frame of `mask` (what change_mask returns) eroded, dilated,
+        opened or closed by a box of radii rx, ry (ry None: rx) or a diamond
+        of radius rx; outside the region counts as clear for a dilation and
+        as set for an erosion.  A mask that lives on the device goes through
+        run_mask_morph_device."""
+        if not isinstance(mask, ChangeMask):
+            raise ValueError("mask must be a ChangeMask")
+        bits = np.ascontiguousarray(mask.bits, dtype=np.uint8)
+        rw = int(mask.width)
+        if bits.ndim != 3 or rw < 0 or bits.shape[2] != 4 * ((rw + 31) // 32):
+            raise ValueError("mask.bits must be [n, h, 4 * ceil(width / 32)] bytes")
+        n, rh = int(bits.shape[0]), int(bits.shape[1])
+        op, shape, rx, ry = _morph_args(op, shape, rx, ry, rw, rh)
+        out = np.zeros_like(bits)
+        self._host.check(self._host._lib.dips_mask_morph(
+            self._host.ptr, bits.ctypes.data if n else None, n, rw, rh, op, shape, rx, ry,
+            out.ctypes.data if n else None))
+        return ChangeMask(out, rw)
+
+    def run_mask_morph_device(self, mask, width: int, out, op, rx: int = 1, ry: Optional[int] = None,
+                              shape=MorphShape.Box, stream=None) -> None:
+        """Asynchronous: mask and out uint8 device tensors [N, h, row_bytes]
+        as run_change_mask_device writes them for a region `width` pixels
+        wide, 4-byte aligned and not overlapping; every byte of out is
+        written."""
+        import torch
+        rw = int(width)
+        for t in (mask, out):
+            if t.dim() != 3 or rw < 0 or t.shape[2] != 4 * ((rw + 31) // 32) or t.dtype != torch.uint8:
+                raise ValueError("mask and out must be uint8 tensors of shape [N, h, 4 * ceil(width / 32)]")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device path needs contiguous HIP tensors")
+        if tuple(out.shape) != tuple(mask.shape):
+            raise ValueError("out must have the shape of mask")
+        n, rh = int(mask.shape[0]), int(mask.shape[1])
+        op, shape, rx, ry = _morph_args(op, shape, rx, ry, rw, rh)
+        nbytes = mask.numel()
+        if n and mask.data_ptr() < out.data_ptr() + nbytes and out.data_ptr() < mask.data_ptr() + nbytes:
+            raise ValueError("mask and out must not overlap")
+        if n and ((mask.data_ptr() | out.data_ptr()) & 3) != 0:
+            raise ValueError("mask and out must be 4-byte aligned")
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_morph(
+                self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, op, shape, rx, ry,
+                out.data_ptr() if n else None))
+
     def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
-                     max_boxes: int = 64, labels: bool = False) -> ChangeBoxes:
+                     max_boxes: int = 64, labels: bool = False, morph=None) -> ChangeBoxes:
         """change_mask, then mask_components, with the mask kept on the
         device between the two: the moving objects of every frame.  frames /
-        ref: numpy arrays (uploaded once) or uint8 device tensors."""
+        ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
+        sequence of (op, shape, rx, ry) steps of mask_morph applied in order
+        to the mask before its components are taken (None: none)."""
         import torch
         dev = torch.device("cuda", self._dev.device)
 
@@ -937,6 +1032,7 @@ class DiffSeriesOperator:
         n, h, w = _frame_geometry(frames, self.fmt)
         rh, rw = self._region(roi, h, w)
         _, _, k, _ = _components_args(connectivity, min_area, max_boxes, 0, n)
+        steps = _morph_steps(morph, rw, rh) if morph is not None else []
         if ref is not None:
             ref = ref.reshape(-1)
         mask = torch.empty((n, rh, 4 * ((rw + 31) // 32)), dtype=torch.uint8, device=dev)
@@ -944,6 +1040,11 @@ class DiffSeriesOperator:
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
         lab = torch.empty((n, rh, rw), dtype=torch.int32, device=dev) if labels else None
         self.run_change_mask_device(frames, mask, roi=roi, ref=ref)
+        if steps:
+            other = torch.empty_like(mask)
+            for op_, shape_, rx_, ry_ in steps:  # ping-pong: the newest mask is `mask`
+                self.run_mask_morph_device(mask, rw, other, op_, rx_, ry_, shape_)
+                mask, other = other, mask
         self.run_mask_components_device(mask, rw, counts, boxes, lab, connectivity=connectivity, min_area=min_area)
 
         def to_u32(t):

@@ -319,6 +319,22 @@ struct ComponentsArgs {
     uint32_t max_boxes;
 };
 
+// The binary morphology of a batch of change-mask frames (mask_morph.hip):
+// one launch, tiles of the frames as a flattened 64-bit index.
+struct MorphArgs {
+    const uint32_t* in;   // n_frames frames of h * wpr words
+    uint32_t* out;        // the same layout; every word is written, pad bits 0
+    uint64_t items;       // n_frames * tiles_x * tiles_y
+    uint32_t w, h;
+    uint32_t wpr;         // mask words per row
+    uint32_t n_frames;
+    uint32_t op;          // DIPS_MORPH_ERODE .. DIPS_MORPH_CLOSE
+    uint32_t shape;       // DIPS_MORPH_BOX or DIPS_MORPH_DIAMOND (then ry == rx)
+    uint32_t rx, ry;      // <= DIPS_MORPH_MAX_RADIUS
+    uint32_t tiles_x;     // from mask_morph_tiling
+    uint32_t tiles_y;
+};
+
 struct SynthArgs {
     uint8_t* dst;
     uint64_t total_bytes;
@@ -522,6 +538,10 @@ hipError_t launch_times_generic(const TimesGenericArgs& a, int channels, hipStre
 // the connected components of a chunk of mask frames (mask_components.hip):
 // every launch of the chunk, in order, on `s`
 hipError_t launch_mask_components(const ComponentsArgs& a, hipStream_t s);
+// the binary morphology of mask frames (mask_morph.hip): the one launch of a
+// call on `s`, and the tiles it cuts a w x h frame into
+hipError_t launch_mask_morph(const MorphArgs& a, hipStream_t s);
+void mask_morph_tiling(uint32_t w, uint32_t h, uint32_t* tiles_x, uint32_t* tiles_y);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 hipError_t launch_read_ceiling(const uint8_t* p, uint64_t bytes, uint32_t* out, hipStream_t s);
 // read-only walk in the RGB8 / RGBA8 series kernel's shape (vec_bytes 12 / 16, U = kUnrollV2Rgb / kUnrollV2)

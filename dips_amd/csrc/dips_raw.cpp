@@ -45,6 +45,12 @@
 //            anchor,cx256,cy256, one row per stored record, and a line
 //            "# frame,count" per frame (count is not capped by K); stdout one
 //            line with the region, the frames, the components and the records
+//            [--morph erode|dilate|open|close:box|diamond:RXxRY]... -> with
+//            --mask or --boxes: the binary morphology of the change mask with
+//            dips_mask_morph (radii 0 .. 15, a diamond needs RX = RY), the steps
+//            applied in the order given; --mask then writes the cleaned mask
+//            and --boxes takes the components of the cleaned mask, and the
+//            stdout line ends with morph=<steps>
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -111,6 +117,7 @@ int usage() {
                  "                [--chunk N] [--grid RxC [--roi x,y,w,h]] [--pixel-sums FILE [--roi x,y,w,h]]\n"
                  "                [--mask FILE [--roi x,y,w,h]] [--pixel-times FILE [--roi x,y,w,h]]\n"
                  "                [--boxes FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
+                 "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask or --boxes)\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -143,6 +150,42 @@ bool parse_grid(const std::string& s, uint32_t* rows, uint32_t* cols) {
     const size_t x = s.find('x');
     if (x == std::string::npos) return false;
     return parse_u32(s.substr(0, x).c_str(), rows) && parse_u32(s.substr(x + 1).c_str(), cols);
+}
+
+// One step of --morph: the arguments of dips_mask_morph.
+struct MorphStep {
+    uint32_t op, shape, rx, ry;
+};
+
+// "OP:SHAPE:RXxRY" -> a step (radii 0 .. DIPS_MORPH_MAX_RADIUS, a diamond with RX = RY)
+bool parse_morph(const std::string& s, MorphStep* m) {
+    const size_t c1 = s.find(':'), c2 = c1 == std::string::npos ? c1 : s.find(':', c1 + 1);
+    if (c2 == std::string::npos) return false;
+    const std::string op = s.substr(0, c1), shape = s.substr(c1 + 1, c2 - c1 - 1), radii = s.substr(c2 + 1);
+    const size_t x = radii.find('x');
+    if (x == std::string::npos) return false;
+    m->op = op == "erode" ? DIPS_MORPH_ERODE : op == "dilate" ? DIPS_MORPH_DILATE : op == "open" ? DIPS_MORPH_OPEN
+                                                                                                  : DIPS_MORPH_CLOSE;
+    if (m->op == DIPS_MORPH_CLOSE && op != "close") return false;
+    if (shape != "box" && shape != "diamond") return false;
+    m->shape = shape == "box" ? DIPS_MORPH_BOX : DIPS_MORPH_DIAMOND;
+    if (!parse_u32_or_zero(radii.substr(0, x).c_str(), &m->rx) || !parse_u32_or_zero(radii.substr(x + 1).c_str(), &m->ry))
+        return false;
+    if (m->rx > DIPS_MORPH_MAX_RADIUS || m->ry > DIPS_MORPH_MAX_RADIUS) return false;
+    return m->shape == DIPS_MORPH_BOX || m->rx == m->ry;
+}
+
+// The steps in order on the host mask of n frames of rw x rh pixels; the
+// result is in `mask` again.
+int apply_morph(dips_handle* hd, std::vector<uint8_t>& mask, uint32_t n, uint32_t rw, uint32_t rh,
+                const std::vector<MorphStep>& steps) {
+    std::vector<uint8_t> other(steps.empty() ? 0u : mask.size());
+    for (const MorphStep& m : steps) {
+        const int st = dips_mask_morph(hd, mask.data(), n, rw, rh, m.op, m.shape, m.rx, m.ry, other.data());
+        if (st != DIPS_OK) return st;
+        mask.swap(other);
+    }
+    return DIPS_OK;
 }
 
 // "x,y,w,h" -> roi[4] (decimal, zero allowed; the library checks the extent)
@@ -420,6 +463,7 @@ int run_series(int argc, char** argv) {
     const char* boxes_path = nullptr;
     uint32_t connectivity = 8, min_area = 1, max_boxes = 64;
     bool has_box_opt = false;
+    std::vector<MorphStep> morph;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -451,6 +495,10 @@ int run_series(int argc, char** argv) {
             uint32_t* v = a == "--connectivity" ? &connectivity : a == "--min-area" ? &min_area : &max_boxes;
             if (!parse_u32_or_zero(argv[++i], v)) return usage();
             has_box_opt = true;
+        } else if (a == "--morph" && has) {
+            MorphStep m{};
+            if (!parse_morph(argv[++i], &m)) return usage();
+            morph.push_back(m);
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -458,6 +506,8 @@ int run_series(int argc, char** argv) {
             return usage();
         }
     }
+    // --morph belongs to --mask or --boxes
+    if (!morph.empty() && !mask_path && !boxes_path) return usage();
     // --roi belongs to --grid, --pixel-sums, --mask, --pixel-times or --boxes
     if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path && !boxes_path) return usage();
     if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) +
@@ -537,9 +587,14 @@ int run_series(int argc, char** argv) {
                           (uint64_t)rw * rh < (1ull << 30);
         const uint32_t row_bytes = dips_mask_row_bytes(rw);
         std::vector<uint8_t> mask(sane ? (size_t)n * rh * row_bytes : 1u);
+        const char* what = "dips_diff_change_mask";
         st = dips_diff_change_mask(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, mask.data());
+        if (st == DIPS_OK && !morph.empty()) {
+            what = "dips_mask_morph";
+            st = apply_morph(hd, mask, n, rw, rh, morph);
+        }
         if (st != DIPS_OK) {
-            const int rc = lib_error(hd, "dips_diff_change_mask", st);
+            const int rc = lib_error(hd, what, st);
             dips_destroy(hd);
             return rc;
         }
@@ -553,8 +608,10 @@ int run_series(int argc, char** argv) {
         }
         unsigned long long set = 0;
         for (const uint8_t b : mask) set += (unsigned long long)__builtin_popcount(b);
-        std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu\n", has_roi ? roi[0] : 0u,
+        std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu", has_roi ? roi[0] : 0u,
                     has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
+        if (!morph.empty()) std::printf(" morph=%zu", morph.size());
+        std::printf("\n");
         return 0;
     }
     if (boxes_path) {
@@ -568,6 +625,10 @@ int run_series(int argc, char** argv) {
         std::vector<uint32_t> counts(sane ? (size_t)n : 1u), recs(sane ? (size_t)n * max_boxes * DIPS_BOX_WORDS : 1u);
         const char* what = "dips_diff_change_mask";
         st = dips_diff_change_mask(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, mask.data());
+        if (st == DIPS_OK && !morph.empty()) {
+            what = "dips_mask_morph";
+            st = apply_morph(hd, mask, n, rw, rh, morph);
+        }
         if (st == DIPS_OK) {
             what = "dips_mask_components";
             st = dips_mask_components(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, counts.data(),
@@ -599,9 +660,11 @@ int run_series(int argc, char** argv) {
             std::fprintf(stderr, "dips_raw: cannot write %s\n", boxes_path);
             return 1;
         }
-        std::printf("boxes roi=%u,%u,%u,%u frames=%u connectivity=%u min_area=%u max_boxes=%u components=%llu records=%llu\n",
+        std::printf("boxes roi=%u,%u,%u,%u frames=%u connectivity=%u min_area=%u max_boxes=%u components=%llu records=%llu",
                     has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, connectivity, min_area, max_boxes, total,
                     stored);
+        if (!morph.empty()) std::printf(" morph=%zu", morph.size());
+        std::printf("\n");
         return 0;
     }
     if (times_path) {

@@ -1068,6 +1068,46 @@ dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t 
     return DIPS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The binary morphology of a mask (dips_mask_morph; kernel in mask_morph.hip)
+// ---------------------------------------------------------------------------
+
+// One launch over the frames of a device mask, asynchronously on `s`.
+dips_status run_morph_device(dips_handle* h, const uint8_t* mask_in, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                             uint32_t op, uint32_t shape, uint32_t rx, uint32_t ry, uint8_t* mask_out,
+                             hipStream_t s) {
+    dips::MorphArgs a{};
+    a.in = reinterpret_cast<const uint32_t*>(mask_in);
+    a.out = reinterpret_cast<uint32_t*>(mask_out);
+    a.w = w;
+    a.h = hgt;
+    a.wpr = (uint32_t)mask_words_per_row(w);
+    a.n_frames = n_frames;
+    a.op = op;
+    a.shape = shape;
+    a.rx = rx;
+    a.ry = ry;
+    dips::mask_morph_tiling(w, hgt, &a.tiles_x, &a.tiles_y);
+    a.items = (uint64_t)n_frames * a.tiles_x * a.tiles_y;
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    DIPS_HIP(h, dips::launch_mask_morph(a, s));
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    return DIPS_OK;
+}
+
 // One timed launch of a read-only leg on the handle's stream: *ms = its
 // hipEvent duration (synchronous).
 template <typename Launch>
@@ -1417,6 +1457,45 @@ dips_status dips_mask_components(dips_handle* h, const uint8_t* mask, uint32_t n
         if (max_boxes != 0u)
             DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
         if (labels) DIPS_HIP(h, hipMemcpyAsync(labels, h->stage_map.p, labels_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_morph(dips_handle* h, const uint8_t* mask_in, uint32_t n_frames, uint32_t roi_w,
+                            uint32_t roi_h, uint32_t op, uint32_t shape, uint32_t rx, uint32_t ry,
+                            uint8_t* mask_out) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask_in || !mask_out) return fail(h, DIPS_ERR_INVALID, "mask_morph: null argument");
+        if (op > DIPS_MORPH_CLOSE) return fail(h, DIPS_ERR_INVALID, "mask_morph: op must be 0 .. 3");
+        if (shape > DIPS_MORPH_DIAMOND) return fail(h, DIPS_ERR_INVALID, "mask_morph: shape must be 0 or 1");
+        if (rx > DIPS_MORPH_MAX_RADIUS || ry > DIPS_MORPH_MAX_RADIUS)
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: rx and ry must be 0 .. 15");
+        if (shape == DIPS_MORPH_DIAMOND && ry != rx)
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: a diamond needs ry == rx");
+        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_morph: roi_w and roi_h must not be 0");
+        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: the region must stay below 2^30 pixels");
+        const size_t bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const uintptr_t pi = (uintptr_t)mask_in, po = (uintptr_t)mask_out;
+        if (pi < po + bytes && po < pi + bytes)
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: mask_in and mask_out must not overlap");
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            if (((pi | po) & 3u) != 0)
+                return fail(h, DIPS_ERR_INVALID, "mask_morph: the device pointers must be 4-byte aligned");
+            return run_morph_device(h, mask_in, n_frames, roi_w, roi_h, op, shape, rx, ry, mask_out, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call)
+        DIPS_HIP(h, h->stage_frames.ensure(bytes));
+        DIPS_HIP(h, h->stage_map.ensure(bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask_in, bytes, hipMemcpyHostToDevice, h->stream));
+        st = run_morph_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, op, shape, rx, ry,
+                              h->stage_map.as<uint8_t>(), h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

@@ -449,6 +449,58 @@ dips_status dips_mask_components(dips_handle *h, const uint8_t *mask, uint32_t n
                                  uint32_t chunk_frames,
                                  uint32_t *counts, uint32_t *boxes, uint32_t *labels);
 
+/* The binary morphology of a change mask, frame by frame: the cleanup
+ * between threshold and components (difference -> threshold -> morphology ->
+ * components -> boxes).  The reference has no counterpart.  A second stage
+ * like dips_mask_components: it reads a mask and writes a mask, so it serves
+ * every pixel format, and the answer is exact.
+ * Input and output: both in exactly dips_diff_change_mask's layout --
+ * n_frames frames of roi_h rows of dips_mask_row_bytes(roi_w) bytes, bit i of
+ * a row = bit (i & 31) of little-endian word i >> 5.  The pad bits of the
+ * input are ignored, whatever they hold; those of the output are written as
+ * 0, and every byte of mask_out is written.  Frames are independent, and so
+ * are rows' ends: nothing reaches from the last row of frame t into frame
+ * t + 1, or from a row's end into the next row.
+ * Structuring element B (symmetric): DIPS_MORPH_BOX {(dx, dy): |dx| <= rx,
+ * |dy| <= ry}; DIPS_MORPH_DIAMOND {(dx, dy): |dx| + |dy| <= rx}, ry must
+ * equal rx.  With X the set pixels of one frame inside the region D =
+ * [0, roi_w) x [0, roi_h):
+ *   dilate(X) = {p in D: some b in B has p + b in X}   (outside D is clear)
+ *   erode(X)  = {p in D: every b in B with p + b in D has p + b in X}
+ *               (outside D counts as set: B is clipped to the region)
+ *   open = erode, then dilate;  close = dilate, then erode.
+ * This is OpenCV's default border (scipy: binary_dilation(border_value=0),
+ * binary_erosion(border_value=1)).  It makes the two an adjunction on the
+ * subsets of D: erode(X) = D \ dilate(D \ X), open(X) <= X <= close(X), open
+ * and close are idempotent, a frame of all ones erodes to all ones.  The
+ * diamond of radius r equals r applications of the diamond of radius 1.
+ * rx = ry = 0 copies the mask with the pad bits zeroed; a radius larger than
+ * the region is legal.  DIPS_MORPH_MAX_RADIUS is 15 so that open and close
+ * reach 2 * 15 = 30 < 32 bits sideways and a word depends on its two
+ * neighbour words only; larger boxes compose from two calls.
+ * One kernel launch per call, no scratch; the time does not
+ * depend on the bits.
+ * DIPS_FLAG_DEVICE_PTRS: both pointers are device pointers, 4-byte aligned,
+ * the call asynchronous on the handle's stream; else host pointers of any
+ * alignment, staged through HBM, synchronous.  DIPS_FLAG_TIME_KERNEL: one
+ * entry for all launches of the call.  n_frames == 0: DIPS_OK, nothing
+ * written.  DIPS_ERR_INVALID, mask_out untouched: a null pointer with
+ * n_frames > 0, a misaligned device pointer, op > 3, shape > 1, rx or ry >
+ * DIPS_MORPH_MAX_RADIUS, a diamond with ry != rx, roi_w or roi_h of 0, a
+ * region of 2^30 pixels or more, and input and output byte ranges that
+ * overlap at all (in place is refused, not silently wrong). */
+#define DIPS_MORPH_ERODE 0u
+#define DIPS_MORPH_DILATE 1u
+#define DIPS_MORPH_OPEN 2u    /* erode, then dilate */
+#define DIPS_MORPH_CLOSE 3u   /* dilate, then erode */
+#define DIPS_MORPH_BOX 0u     /* B = {(dx, dy): |dx| <= rx, |dy| <= ry} */
+#define DIPS_MORPH_DIAMOND 1u /* B = {(dx, dy): |dx| + |dy| <= rx}; ry must equal rx */
+#define DIPS_MORPH_MAX_RADIUS 15u
+dips_status dips_mask_morph(dips_handle *h, const uint8_t *mask_in, uint32_t n_frames,
+                            uint32_t roi_w, uint32_t roi_h,
+                            uint32_t op, uint32_t shape, uint32_t rx, uint32_t ry,
+                            uint8_t *mask_out);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,

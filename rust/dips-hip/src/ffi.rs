@@ -47,6 +47,13 @@ pub const DIPS_COMM_RCCL: c_int = 1;
 pub const DIPS_COMM_LOOPBACK: c_int = 2;
 pub const DIPS_COMM_HOST: c_int = 3;
 pub const DIPS_SHARD_REF_RESIDENT: u32 = 0x1;
+pub const DIPS_MORPH_ERODE: u32 = 0;
+pub const DIPS_MORPH_DILATE: u32 = 1;
+pub const DIPS_MORPH_OPEN: u32 = 2;
+pub const DIPS_MORPH_CLOSE: u32 = 3;
+pub const DIPS_MORPH_BOX: u32 = 0;
+pub const DIPS_MORPH_DIAMOND: u32 = 1;
+pub const DIPS_MORPH_MAX_RADIUS: u32 = 15;
 
 /// `dips_params`: ComputeState::new's arguments (dips/src/gpu/mod.rs:59-65,
 /// DiPsProperties dips/src/lib.rs:63-86) + the batch series configuration.
@@ -191,6 +198,8 @@ extern "C" {
     pub fn dips_mask_components(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32,
                                 connectivity: u32, min_area: u32, max_boxes: u32, chunk_frames: u32,
                                 counts: *mut u32, boxes: *mut u32, labels: *mut u32) -> DipsStatus;
+    pub fn dips_mask_morph(h: *mut DipsHandle, mask_in: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, op: u32,
+                           shape: u32, rx: u32, ry: u32, mask_out: *mut u8) -> DipsStatus;
     pub fn dips_synth_frames(h: *mut DipsHandle, width: u32, height: u32, seed: u64, t0: u64, n_frames: u32,
                              dst: *mut u8) -> DipsStatus;
     pub fn dips_kernel_time(h: *mut DipsHandle, total_ms: *mut f64, launches: *mut u64) -> DipsStatus;
