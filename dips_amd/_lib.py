@@ -47,6 +47,8 @@ BOX_FIELDS = ("x0", "y0", "x1", "y1", "area", "anchor", "cx256", "cy256")
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # DIPS_MORPH_ERODE .. DIPS_MORPH_CLOSE
 MORPH_BOX, MORPH_DIAMOND = 0, 1  # DIPS_MORPH_BOX, DIPS_MORPH_DIAMOND
 MORPH_MAX_RADIUS = 15  # DIPS_MORPH_MAX_RADIUS
+BG_SELECTIVE = 1  # DIPS_BG_SELECTIVE
+BG_MAX_RATE_SHIFT = 8  # DIPS_BG_MAX_RATE_SHIFT
 
 COMM_ID_BYTES = 128
 COMM_RCCL = 1
@@ -190,6 +192,7 @@ def load() -> ctypes.CDLL:
             "dips_mask_row_bytes": ([u32], u32),
             "dips_diff_change_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), _u8p], st),
             "dips_diff_pixel_times": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, _vp], st),
+            "dips_diff_background_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, u32, _vp, _u8p], st),
             "dips_mask_components": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _vp, _vp, _vp], st),
             "dips_mask_morph": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),

@@ -544,6 +544,35 @@ class PixelTimes:
 
 
 @dataclass
+class Background:
+    """The running-average background of a region
+    (dips_diff_background_mask): `state` uint16 [C, h, w], per channel plane
+    the average in 8.8 fixed point (0 .. 65280)."""
+    state: np.ndarray
+
+    def image(self) -> np.ndarray:
+        """uint8 [h, w, C]: the background rounded to bytes, (state + 128) >>
+        8 -- what the decision compares a frame with; a `ref` for every other
+        product of the same region."""
+        r = (self.state.astype(np.uint32) + 128) >> 8
+        return np.ascontiguousarray(np.moveaxis(r, 0, -1).astype(np.uint8))
+
+    @classmethod
+    def from_array(cls, a: np.ndarray) -> "Background":
+        a = np.ascontiguousarray(a, dtype=np.uint16)
+        if a.ndim != 3 or a.shape[0] not in (1, 3, 4):
+            raise ValueError("background state must be [C, h, w] with C of 1, 3 or 4")
+        return cls(a)
+
+
+def _background_args(rate_shift, selective) -> Tuple[int, int]:
+    """rate_shift and bg_flags of dips_diff_background_mask, checked."""
+    if isinstance(rate_shift, bool) or int(rate_shift) != rate_shift or not 0 <= int(rate_shift) <= _lib.BG_MAX_RATE_SHIFT:
+        raise ValueError(f"rate_shift must be an integer 0 .. {_lib.BG_MAX_RATE_SHIFT}")
+    return int(rate_shift), _lib.BG_SELECTIVE if selective else 0
+
+
+@dataclass
 class ChangeBoxes:
     """The connected components of a change mask (dips_mask_components):
     `counts` uint32 [n], the kept components per frame (not capped by K);
@@ -900,6 +929,79 @@ class DiffSeriesOperator:
                 ref.data_ptr() if ref is not None else None, _roi_arg(roi),
                 mask_out.data_ptr() if mask_out.numel() else None))
 
+    # -- the running-average background (dips_diff_background_mask) ----------
+    def background_mask(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None, rate_shift: int = 3,
+                        selective: bool = False, state: Optional[Background] = None) -> Tuple[ChangeMask, Background]:
+        """The change mask of every frame against a per-pixel running average
+        of the frames before it (update rate 2^-rate_shift; selective: pixels
+        that changed do not update), and the average after the last frame.
+        The average starts at `ref` (None: frame 0) or continues `state`, the
+        Background an earlier call over the same region returned -- a clip in
+        chunks.  The operator's mode is not consulted."""
+        frames = _as_u8(frames)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        c = int(self.fmt)
+        k, flags = _background_args(rate_shift, selective)
+        if state is not None:
+            if ref is not None:
+                raise ValueError("ref and state exclude each other")
+            if not isinstance(state, Background):
+                raise ValueError("state must be a Background")
+            bg = np.array(state.state, dtype=np.uint16, order="C")
+            if bg.shape != (c, rh, rw):
+                raise ValueError("state must hold the background of the same region and format")
+        else:
+            if ref is None and n == 0:
+                raise ValueError("the initial background needs ref or a frame")
+            bg = np.zeros((c, rh, rw), dtype=np.uint16)
+        out = np.zeros((n, rh, 4 * ((rw + 31) // 32)), dtype=np.uint8)
+        rp = None
+        if ref is not None:
+            ref = _as_u8(ref)
+            if ref.size != h * w * c:
+                raise ValueError("ref must have the shape of one frame")
+            rp = ref.ctypes.data
+        self._host.check(self._host._lib.dips_diff_background_mask(
+            self._host.ptr, w, h, frames.ctypes.data if n else None, n, rp, _roi_arg(roi), k, flags,
+            1 if state is not None else 0, bg.ctypes.data, out.ctypes.data if out.size else None))
+        return ChangeMask(out, rw), Background(bg)
+
+    def run_background_mask_device(self, frames, background, mask_out=None, roi=None, ref=None, rate_shift: int = 3,
+                                   selective: bool = False, accumulate: bool = False, stream=None) -> None:
+        """Asynchronous: frames / ref uint8 device tensors, background a
+        2-byte device tensor of shape [C, h, w] of the region, overwritten or
+        (accumulate: ref must be None) continued; mask_out a uint8 device
+        tensor of shape [N, h, row_bytes] of the region (4-byte aligned),
+        every byte of which is written, or None for the background alone."""
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        c = int(self.fmt)
+        k, flags = _background_args(rate_shift, selective)
+        if tuple(background.shape) != (c, rh, rw) or background.element_size() != 2:
+            raise ValueError("background must be a 2-byte tensor of shape [C, h, w] of the region")
+        if mask_out is not None and tuple(mask_out.shape) != (n, rh, 4 * ((rw + 31) // 32)):
+            raise ValueError("mask_out must be a uint8 tensor of shape [N, h, 4 * ceil(w / 32)] of the region")
+        for t in (frames, background, mask_out, ref):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        import torch
+        for t in (frames, mask_out, ref):
+            if t is not None and t.dtype != torch.uint8:
+                raise ValueError("frames, ref and mask_out must be uint8 tensors")
+        if ref is not None and ref.numel() != h * w * c:
+            raise ValueError("ref must have the size of one frame")
+        if accumulate and ref is not None:
+            raise ValueError("ref and accumulate exclude each other")
+        if not accumulate and ref is None and n == 0:
+            raise ValueError("the initial background needs ref or a frame")
+        lib = self._dev._lib
+        with _stream_of(self._dev, frames, stream):
+            self._dev.check(lib.dips_diff_background_mask(
+                self._dev.ptr, w, h, frames.data_ptr() if n else None, n,
+                ref.data_ptr() if ref is not None else None, _roi_arg(roi), k, flags, 1 if accumulate else 0,
+                background.data_ptr(), mask_out.data_ptr() if mask_out is not None and mask_out.numel() else None))
+
     # -- the connected components of a change mask (dips_mask_components) ----
     def mask_components(self, mask: ChangeMask, connectivity: int = 8, min_area: int = 1, max_boxes: int = 64,
                         labels: bool = False, chunk_frames: int = 0) -> ChangeBoxes:
@@ -1014,12 +1116,15 @@ class DiffSeriesOperator:
                 out.data_ptr() if n else None))
 
     def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
-                     max_boxes: int = 64, labels: bool = False, morph=None) -> ChangeBoxes:
+                     max_boxes: int = 64, labels: bool = False, morph=None, background=None) -> ChangeBoxes:
         """change_mask, then mask_components, with the mask kept on the
         device between the two: the moving objects of every frame.  frames /
         ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
         sequence of (op, shape, rx, ry) steps of mask_morph applied in order
-        to the mask before its components are taken (None: none)."""
+        to the mask before its components are taken (None: none).
+        background: None, or rate_shift or (rate_shift, selective) to take
+        the mask against the running-average background (background_mask)
+        instead of the operator's mode."""
         import torch
         dev = torch.device("cuda", self._dev.device)
 
@@ -1033,13 +1138,22 @@ class DiffSeriesOperator:
         rh, rw = self._region(roi, h, w)
         _, _, k, _ = _components_args(connectivity, min_area, max_boxes, 0, n)
         steps = _morph_steps(morph, rw, rh) if morph is not None else []
+        if background is not None:
+            bg_k, bg_sel = background if isinstance(background, (tuple, list)) else (background, False)
+            _background_args(bg_k, bg_sel)
+            if n == 0 and ref is None:
+                raise ValueError("the initial background needs ref or a frame")
         if ref is not None:
             ref = ref.reshape(-1)
         mask = torch.empty((n, rh, 4 * ((rw + 31) // 32)), dtype=torch.uint8, device=dev)
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
         lab = torch.empty((n, rh, rw), dtype=torch.int32, device=dev) if labels else None
-        self.run_change_mask_device(frames, mask, roi=roi, ref=ref)
+        if background is None:
+            self.run_change_mask_device(frames, mask, roi=roi, ref=ref)
+        else:
+            bg = torch.empty((int(self.fmt), rh, rw), dtype=torch.int16, device=dev)
+            self.run_background_mask_device(frames, bg, mask, roi=roi, ref=ref, rate_shift=bg_k, selective=bg_sel)
         if steps:
             other = torch.empty_like(mask)
             for op_, shape_, rx_, ry_ in steps:  # ping-pong: the newest mask is `mask`
@@ -1258,7 +1372,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "mask_row_bytes", "grid_cell",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "Background", "mask_row_bytes", "grid_cell",
     "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",

@@ -290,6 +290,56 @@ struct TimesGenericArgs {
     GridRect rect;
 };
 
+// series_background_kernel (series_background.hip): the running-average
+// background of a region and the change mask against it.  The mask kernel's
+// geometry (rows padded to 8 vecs per mask word), one part always: a wave
+// owns every frame of its tile, with the state of its pixels -- a u16 per
+// channel -- in registers.
+#ifndef DIPS_UNROLL_BACKGROUND
+#define DIPS_UNROLL_BACKGROUND 2
+#endif
+constexpr int kUnrollBackground = DIPS_UNROLL_BACKGROUND;  // vecs per lane: 512 px / wave / frame
+struct BgArgs {
+    const uint8_t* frames;   // n_frames * frame_bytes, contiguous
+    const uint8_t* ref0;     // accumulate == 0: the initial state is 256 * its bytes
+    uint16_t* background;    // C planes of roi.w * roi.h u16, 2-byte aligned
+    uint8_t* mask;           // n_frames * mask_frame_bytes, 4-byte aligned, or NULL
+    uint32_t frame_bytes;
+    uint32_t mask_frame_bytes;  // roi.h * 4 * ceil(roi.w / 32)
+    uint32_t width;          // frame width in pixels (the row pitch)
+    uint32_t n_frames;       // >= 1
+    uint32_t n_tiles;
+    uint32_t n_waves;
+    uint32_t rate_shift;     // 0 .. 8
+    uint32_t selective;      // DIPS_BG_SELECTIVE set
+    uint32_t accumulate;     // continue the state `background` holds
+    float thr;               // series_threshold(C, tau, 0)
+    GridRect roi;
+};
+
+// background_generic_kernel: one thread per mask word of rows [row0, row0 +
+// n_rows) x words [word0, word0 + n_words) of the region walks the word's
+// pixels and, per pixel, the frames; it stores the state of the pixels from
+// region column state_x0 on.  n_frames may be 0 (the initial state alone).
+struct BgGenericArgs {
+    const uint8_t* frames;
+    const uint8_t* ref0;
+    uint16_t* background;
+    uint8_t* mask;           // or NULL
+    uint64_t frame_bytes;
+    uint64_t mask_frame_bytes;
+    uint32_t width;
+    uint32_t n_frames;
+    uint32_t chroma;
+    float tau;
+    uint32_t rate_shift;
+    uint32_t selective;
+    uint32_t accumulate;
+    uint32_t row0, n_rows, word0, n_words;
+    uint32_t state_x0;
+    GridRect roi;
+};
+
 // The connected components of a chunk of change-mask frames
 // (mask_components.hip).  Scratch per frame: parent, one u32 per pixel, and
 // the statistics of the word-local runs, one slot per two pixels of a row.
@@ -535,6 +585,13 @@ hipError_t launch_series_times(const TimesArgs& a, int channels, int chroma, boo
                                uint32_t blocks, hipStream_t s);
 hipError_t launch_times_combine(const TimesCombineArgs& a, hipStream_t s);
 hipError_t launch_times_generic(const TimesGenericArgs& a, int channels, hipStream_t s);
+// the running-average background and its change mask (series_background.hip):
+// RGB8 / RGBA8 fast kernel (tiles of kUnrollBackground vecs per lane, or of
+// one for small regions) and the any-format generic kernel
+const void* series_background_kernel_ptr(int channels, int chroma, bool small_tile);
+hipError_t launch_series_background(const BgArgs& a, int channels, int chroma, bool small_tile, uint32_t blocks,
+                                    hipStream_t s);
+hipError_t launch_background_generic(const BgGenericArgs& a, int channels, hipStream_t s);
 // the connected components of a chunk of mask frames (mask_components.hip):
 // every launch of the chunk, in order, on `s`
 hipError_t launch_mask_components(const ComponentsArgs& a, hipStream_t s);

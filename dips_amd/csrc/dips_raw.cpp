@@ -51,6 +51,13 @@
 //            applied in the order given; --mask then writes the cleaned mask
 //            and --boxes takes the components of the cleaned mask, and the
 //            stdout line ends with morph=<steps>
+//            [--background K[,selective] [--background-out FILE]] -> with
+//            --mask or --boxes: the mask is taken against the running-average
+//            background with dips_diff_background_mask (rate_shift K in
+//            0 .. 8, starting at frame 0) instead of --mode's reference;
+//            --background-out gets the final state, channel planes of roi_h x
+//            roi_w little-endian u16, and the stdout line ends with
+//            background=K[,selective]
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -118,6 +125,7 @@ int usage() {
                  "                [--mask FILE [--roi x,y,w,h]] [--pixel-times FILE [--roi x,y,w,h]]\n"
                  "                [--boxes FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
                  "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask or --boxes)\n"
+                 "                [--background K[,selective] [--background-out FILE]] (with --mask or --boxes)\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -173,6 +181,50 @@ bool parse_morph(const std::string& s, MorphStep* m) {
         return false;
     if (m->rx > DIPS_MORPH_MAX_RADIUS || m->ry > DIPS_MORPH_MAX_RADIUS) return false;
     return m->shape == DIPS_MORPH_BOX || m->rx == m->ry;
+}
+
+// --background: rate_shift and flags of dips_diff_background_mask.
+struct BackgroundOpt {
+    bool on = false;
+    uint32_t rate_shift = 0, flags = 0;
+    const char* out_path = nullptr;
+};
+
+bool parse_background(const std::string& s, BackgroundOpt* b) {
+    const size_t comma = s.find(',');
+    if (comma != std::string::npos && s.substr(comma + 1) != "selective") return false;
+    if (!parse_u32_or_zero(s.substr(0, comma).c_str(), &b->rate_shift) || b->rate_shift > DIPS_BG_MAX_RATE_SHIFT)
+        return false;
+    b->flags = comma != std::string::npos ? DIPS_BG_SELECTIVE : 0u;
+    b->on = true;
+    return true;
+}
+
+// The region's mask for --mask and --boxes: dips_diff_change_mask, or with
+// --background dips_diff_background_mask, whose final state goes to `state`.
+int region_mask(dips_handle* hd, uint32_t w, uint32_t h, const uint8_t* frames, uint32_t n, const uint32_t* roi,
+                const BackgroundOpt& bg, std::vector<uint16_t>& state, uint8_t* mask, const char** what) {
+    if (!bg.on) {
+        *what = "dips_diff_change_mask";
+        return dips_diff_change_mask(hd, w, h, frames, n, nullptr, roi, mask);
+    }
+    *what = "dips_diff_background_mask";
+    return dips_diff_background_mask(hd, w, h, frames, n, nullptr, roi, bg.rate_shift, bg.flags, 0u, state.data(), mask);
+}
+
+// The final background state as raw u16 planes (0: written or not asked for).
+int write_background(const BackgroundOpt& bg, const std::vector<uint16_t>& state) {
+    if (!bg.out_path) return 0;
+    std::FILE* f = std::fopen(bg.out_path, "wb");
+    if (!f || std::fwrite(state.data(), sizeof(uint16_t), state.size(), f) != state.size() || std::fclose(f) != 0) {
+        std::fprintf(stderr, "dips_raw: cannot write %s\n", bg.out_path);
+        return 1;
+    }
+    return 0;
+}
+
+void print_background(const BackgroundOpt& bg) {
+    if (bg.on) std::printf(" background=%u%s", bg.rate_shift, bg.flags ? ",selective" : "");
 }
 
 // The steps in order on the host mask of n frames of rw x rh pixels; the
@@ -464,6 +516,7 @@ int run_series(int argc, char** argv) {
     uint32_t connectivity = 8, min_area = 1, max_boxes = 64;
     bool has_box_opt = false;
     std::vector<MorphStep> morph;
+    BackgroundOpt bg;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -499,6 +552,10 @@ int run_series(int argc, char** argv) {
             MorphStep m{};
             if (!parse_morph(argv[++i], &m)) return usage();
             morph.push_back(m);
+        } else if (a == "--background" && has) {
+            if (!parse_background(argv[++i], &bg)) return usage();
+        } else if (a == "--background-out" && has) {
+            bg.out_path = argv[++i];
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -508,6 +565,8 @@ int run_series(int argc, char** argv) {
     }
     // --morph belongs to --mask or --boxes
     if (!morph.empty() && !mask_path && !boxes_path) return usage();
+    // --background belongs to --mask or --boxes, --background-out to --background
+    if ((bg.on && !mask_path && !boxes_path) || (bg.out_path && !bg.on)) return usage();
     // --roi belongs to --grid, --pixel-sums, --mask, --pixel-times or --boxes
     if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path && !boxes_path) return usage();
     if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) +
@@ -587,8 +646,9 @@ int run_series(int argc, char** argv) {
                           (uint64_t)rw * rh < (1ull << 30);
         const uint32_t row_bytes = dips_mask_row_bytes(rw);
         std::vector<uint8_t> mask(sane ? (size_t)n * rh * row_bytes : 1u);
-        const char* what = "dips_diff_change_mask";
-        st = dips_diff_change_mask(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, mask.data());
+        std::vector<uint16_t> state(sane && bg.on ? (size_t)p.format * rw * rh : 1u);
+        const char* what = nullptr;
+        st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, state, mask.data(), &what);
         if (st == DIPS_OK && !morph.empty()) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
@@ -600,6 +660,7 @@ int run_series(int argc, char** argv) {
         }
         dips_destroy(hd);
         if (n == 0) mask.clear();
+        if (write_background(bg, state) != 0) return 1;
         // frames x roi_h x row_bytes, bit i of a row = bit (i & 7) of byte (i >> 3)
         std::FILE* f = std::fopen(mask_path, "wb");
         if (!f || std::fwrite(mask.data(), 1, mask.size(), f) != mask.size() || std::fclose(f) != 0) {
@@ -611,6 +672,7 @@ int run_series(int argc, char** argv) {
         std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu", has_roi ? roi[0] : 0u,
                     has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
+        print_background(bg);
         std::printf("\n");
         return 0;
     }
@@ -623,8 +685,9 @@ int run_series(int argc, char** argv) {
                           (uint64_t)n * max_boxes * DIPS_BOX_WORDS < (1ull << 32);
         std::vector<uint8_t> mask(sane ? (size_t)n * rh * dips_mask_row_bytes(rw) : 1u);
         std::vector<uint32_t> counts(sane ? (size_t)n : 1u), recs(sane ? (size_t)n * max_boxes * DIPS_BOX_WORDS : 1u);
-        const char* what = "dips_diff_change_mask";
-        st = dips_diff_change_mask(hd, w, h, in.p, n, nullptr, has_roi ? roi : nullptr, mask.data());
+        std::vector<uint16_t> state(sane && bg.on ? (size_t)p.format * rw * rh : 1u);
+        const char* what = nullptr;
+        st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, state, mask.data(), &what);
         if (st == DIPS_OK && !morph.empty()) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
@@ -640,6 +703,7 @@ int run_series(int argc, char** argv) {
             return rc;
         }
         dips_destroy(hd);
+        if (write_background(bg, state) != 0) return 1;
         std::FILE* f = std::fopen(boxes_path, "w");
         if (!f) {
             std::fprintf(stderr, "dips_raw: cannot write %s\n", boxes_path);
@@ -664,6 +728,7 @@ int run_series(int argc, char** argv) {
                     has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, connectivity, min_area, max_boxes, total,
                     stored);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
+        print_background(bg);
         std::printf("\n");
         return 0;
     }

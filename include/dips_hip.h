@@ -394,6 +394,46 @@ dips_status dips_diff_pixel_times(dips_handle *h, uint32_t width, uint32_t heigh
                                   const uint32_t *roi, uint32_t t0, uint32_t accumulate,
                                   uint32_t *times);
 
+/* The running-average background model of a region of interest and the
+ * change mask taken against it: a reference that adapts, where 'overall'
+ * breaks under drifting light and 'per-frame' sees only the edges of a moving
+ * object.  The reference has no counterpart.  Exact and integer.
+ * State: per region pixel and channel c < C (RGBA8's alpha is tracked like
+ * any channel) a u16 B in 8.8 fixed point, 0 <= B <= 65280.  rate_shift k in
+ * 0 .. 8 gives the update rate 2^-k.  For frame t, in order, per pixel:
+ *   R[c]  = (B[c] + 128) >> 8                  the reference bytes (<= 255)
+ *   bit(t, j, i) = dips_diff_change_mask's bit of the single frame F_t in
+ *                  'overall' mode with reference R: strict compare, the same
+ *                  tau and chroma_filter; params.mode is not consulted
+ *   B'[c] = B[c] - ((B[c] + h) >> k) + (F[c] << (8 - k)),  h = (1 << k) >> 1
+ * the update skipped for the whole pixel when bg_flags has DIPS_BG_SELECTIVE
+ * and bit = 1 (foreground is not absorbed).  B = 256 F is a fixed point, for
+ * a static input R settles on F exactly, and k = 0 gives B' = 256 F: the mask
+ * is then dips_diff_change_mask's in 'per-frame' mode with the same ref.
+ * accumulate == 0: the initial state is B = 256 ref (ref == NULL: 256
+ * frames[0], so frame 0 is all zero); with n_frames == 0 the call writes the
+ * initial state (ref is then required).  accumulate != 0: the state
+ * background holds is continued and ref must be NULL; nothing is written when
+ * n_frames == 0.  A clip longer than memory goes chunk by chunk.
+ * Layout of background: C planes of w * h u16, background[c*w*h + j*w + i],
+ * each plane an image; required, 2-byte aligned, written in full.  mask:
+ * exactly dips_diff_change_mask's layout (pad bits 0, every byte written), or
+ * NULL to estimate the background alone.
+ * roi, format, tau, chroma_filter, DIPS_FLAG_DEVICE_PTRS (asynchronous on the
+ * handle's stream; mask 4-byte aligned) and host pointers (staged through
+ * HBM, synchronous, the state uploaded first when accumulating) as in
+ * dips_diff_pixel_times.  DIPS_ERR_INVALID, the outputs untouched, for
+ * rate_shift > 8, unknown bg_flags bits, null frames with n_frames > 0, null
+ * background, ref given with accumulate, no ref and no frames without
+ * accumulate, a misaligned device background or mask, the roi errors of
+ * dips_grid_cell (at rows = cols = 1) and a region of 2^30 pixels or more. */
+#define DIPS_BG_SELECTIVE 1u
+#define DIPS_BG_MAX_RATE_SHIFT 8u
+dips_status dips_diff_background_mask(dips_handle *h, uint32_t width, uint32_t height,
+                                      const uint8_t *frames, uint32_t n_frames, const uint8_t *ref,
+                                      const uint32_t *roi, uint32_t rate_shift, uint32_t bg_flags,
+                                      uint32_t accumulate, uint16_t *background, uint8_t *mask);
+
 /* The connected components of a change mask, frame by frame: the blobs and
  * bounding boxes the README promises the mask "feeds" (difference ->
  * threshold -> components -> boxes).  The reference has no counterpart.  A

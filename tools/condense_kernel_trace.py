@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """condense_kernel_trace.py -- a rocprofv3 --kernel-trace CSV of
-tools/pixel_sums_bench.py, tools/mask_bench.py, tools/pixel_times_bench.py or
-tools/mask_components_bench.py as the compact table kept under profiles/: one row
+tools/pixel_sums_bench.py, tools/mask_bench.py, tools/pixel_times_bench.py,
+tools/mask_components_bench.py or tools/background_bench.py as the compact table kept under profiles/: one row
 per dispatch of the library's series kernels (name, ms, grid, VGPRs as the
 profiler counts them); the torch reduce kernels that follow a map launch are
 summed into one row per call, other kernels are dropped.
@@ -16,7 +16,8 @@ import sys
 OURS = ("series_v2_kernel", "series_reduce_kernel", "series_pixels_kernel", "pixels_generic_kernel",
         "series_mask_kernel", "mask_generic_kernel", "series_times_kernel", "times_combine_kernel",
         "times_generic_kernel", "cc_rows_kernel", "cc_merge_kernel", "cc_stats_kernel", "cc_count_kernel",
-        "cc_offsets_kernel", "cc_select_kernel", "cc_labels_kernel")
+        "cc_offsets_kernel", "cc_select_kernel", "cc_labels_kernel", "series_background_kernel",
+        "background_generic_kernel")
 
 
 def main(src, dst):
