@@ -44,6 +44,10 @@ MODE_PER_FRAME = 1
 TIME_NONE = 0xFFFFFFFF  # DIPS_TIME_NONE
 BOX_WORDS = 8  # DIPS_BOX_WORDS; the fields in the order of DIPS_BOX_X0 .. DIPS_BOX_CY256
 BOX_FIELDS = ("x0", "y0", "x1", "y1", "area", "anchor", "cx256", "cy256")
+LINK_WORDS = 4  # DIPS_LINK_WORDS; the fields in the order of DIPS_LINK_PREV .. DIPS_LINK_AGE
+LINK_FIELDS = ("prev", "overlap", "track", "age")
+LINK_NONE = 0xFFFFFFFF  # DIPS_LINK_NONE
+TRACK_MAX_BOXES = 256  # DIPS_TRACK_MAX_BOXES
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # DIPS_MORPH_ERODE .. DIPS_MORPH_CLOSE
 MORPH_BOX, MORPH_DIAMOND = 0, 1  # DIPS_MORPH_BOX, DIPS_MORPH_DIAMOND
 MORPH_MAX_RADIUS = 15  # DIPS_MORPH_MAX_RADIUS
@@ -194,6 +198,7 @@ def load() -> ctypes.CDLL:
             "dips_diff_pixel_times": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, _vp], st),
             "dips_diff_background_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, u32, _vp, _u8p], st),
             "dips_mask_components": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _vp, _vp, _vp], st),
+            "dips_mask_tracks": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, _vp, _vp, _vp, _vp], st),
             "dips_mask_morph": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),
             "dips_diff_series_streamed": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, u32], st),

@@ -624,6 +624,67 @@ def _components_args(connectivity, min_area, max_boxes, chunk_frames, n: int) ->
     return int(connectivity), int(min_area), int(max_boxes), int(chunk_frames)
 
 
+@dataclass
+class ChangeTracks:
+    """The components of a change mask linked across frames
+    (dips_mask_tracks): `counts` and `boxes` as in ChangeBoxes; `links`
+    uint32 [n, K, 4], per record (FIELDS: prev, overlap, track, age) the
+    record of the frame before it shares the most pixels with (NONE: none)
+    and that overlap, the id of its track and the frames the track has lasted
+    before this one; {NONE, 0, NONE, 0} past min(counts[t], K); `state`
+    uint32 [1 + 2K] (the next unused id, then track and age of the last
+    frame's records: what the next call of a longer clip continues from) or
+    None."""
+    counts: np.ndarray
+    boxes: np.ndarray
+    links: np.ndarray
+    state: Optional[np.ndarray] = None
+
+    FIELDS = _lib.LINK_FIELDS
+    NONE = _lib.LINK_NONE
+
+    def frame(self, t: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(uint32 [m, 8], uint32 [m, 4]): the m = min(counts[t], K) valid
+        records of frame t and their links."""
+        m = min(int(self.counts[t]), self.boxes.shape[1])
+        return self.boxes[t, :m], self.links[t, :m]
+
+    def tracks(self) -> dict:
+        """id -> [(t, k), ...]: the records of every track, in frame order."""
+        out: dict = {}
+        track = _lib.LINK_FIELDS.index("track")
+        for t in range(self.links.shape[0]):
+            for k in range(min(int(self.counts[t]), self.links.shape[1])):
+                out.setdefault(int(self.links[t, k, track]), []).append((t, k))
+        return out
+
+    def as_arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        return self.counts, self.boxes, self.links, self.state
+
+    @classmethod
+    def from_arrays(cls, counts, boxes, links, state=None) -> "ChangeTracks":
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        boxes = np.ascontiguousarray(boxes, dtype=np.uint32)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        if counts.ndim != 1 or boxes.ndim != 3 or boxes.shape[0] != counts.shape[0] or boxes.shape[2] != _lib.BOX_WORDS:
+            raise ValueError("counts must be [n] and boxes [n, K, 8]")
+        if links.shape != boxes.shape[:2] + (_lib.LINK_WORDS,):
+            raise ValueError("links must be [n, K, 4]")
+        if state is not None:
+            state = np.ascontiguousarray(state, dtype=np.uint32)
+            if state.shape != (1 + 2 * boxes.shape[1],):
+                raise ValueError("state must be [1 + 2 * K]")
+        return cls(counts, boxes, links, state)
+
+
+def _tracks_args(connectivity, min_area, max_boxes, chunk_frames, n: int) -> Tuple[int, int, int, int]:
+    """The scalar arguments of dips_mask_tracks, checked."""
+    conn, area, k, chunk = _components_args(connectivity, min_area, max_boxes, chunk_frames, n)
+    if not 1 <= k <= _lib.TRACK_MAX_BOXES:
+        raise ValueError(f"max_boxes must be 1 .. {_lib.TRACK_MAX_BOXES}")
+    return conn, area, k, chunk
+
+
 def _morph_args(op, shape, rx, ry, w: int, h: int) -> Tuple[int, int, int, int]:
     """The scalar arguments of dips_mask_morph, checked; ry None means rx."""
     try:
@@ -1065,6 +1126,90 @@ class DiffSeriesOperator:
                 boxes_out.data_ptr() if boxes_out is not None and boxes_out.numel() else None,
                 labels_out.data_ptr() if labels_out is not None and labels_out.numel() else None))
 
+    # -- the components linked across frames (dips_mask_tracks) ---------------
+    def mask_tracks(self, mask: ChangeMask, connectivity: int = 8, min_area: int = 1, max_boxes: int = 64,
+                    chunk_frames: int = 0, prev: Optional[np.ndarray] = None,
+                    state: Optional[np.ndarray] = None) -> ChangeTracks:
+        """mask_components of every frame of `mask`, and per record its link
+        to the frame before: the record it continues or came from, their
+        overlap, the id and the age of its track.  A longer clip goes call
+        by call: `prev` is the last frame of the previous call's mask
+        (uint8 [h, row_bytes]) and `state` its result's state, and the
+        result equals the one call over the whole clip.  state without prev
+        is a scene cut: the ids go on, the tracks do not.  The returned
+        state is a new array (None when none was given).  A mask that lives
+        on the device goes through run_mask_tracks_device."""
+        if not isinstance(mask, ChangeMask):
+            raise ValueError("mask must be a ChangeMask")
+        bits = np.ascontiguousarray(mask.bits, dtype=np.uint8)
+        rw = int(mask.width)
+        if bits.ndim != 3 or rw < 0 or bits.shape[2] != 4 * ((rw + 31) // 32):
+            raise ValueError("mask.bits must be [n, h, 4 * ceil(width / 32)] bytes")
+        n, rh = int(bits.shape[0]), int(bits.shape[1])
+        conn, area, k, chunk = _tracks_args(connectivity, min_area, max_boxes, chunk_frames, n)
+        if prev is not None:
+            if state is None:
+                raise ValueError("prev needs state")
+            prev = np.ascontiguousarray(prev, dtype=np.uint8)
+            if prev.shape != bits.shape[1:]:
+                raise ValueError("prev must be one frame of the mask: [h, 4 * ceil(width / 32)] bytes")
+        if state is not None:
+            state = np.array(state, dtype=np.uint32)  # a copy: the call writes it
+            if state.shape != (1 + 2 * k,):
+                raise ValueError("state must be [1 + 2 * max_boxes]")
+        counts = np.zeros(n, dtype=np.uint32)
+        boxes = np.zeros((n, k, _lib.BOX_WORDS), dtype=np.uint32)
+        links = np.zeros((n, k, _lib.LINK_WORDS), dtype=np.uint32)
+        self._host.check(self._host._lib.dips_mask_tracks(
+            self._host.ptr, bits.ctypes.data if bits.size else None, n, rw, rh, conn, area, k, chunk,
+            prev.ctypes.data if prev is not None and prev.size else None,
+            state.ctypes.data if state is not None else None,
+            counts.ctypes.data if n else None, boxes.ctypes.data if n else None, links.ctypes.data if n else None))
+        return ChangeTracks(counts, boxes, links, state)
+
+    def run_mask_tracks_device(self, mask, width: int, counts_out, boxes_out, links_out, prev=None, state=None,
+                               connectivity: int = 8, min_area: int = 1, chunk_frames: int = 0, stream=None) -> None:
+        """Asynchronous: mask a uint8 device tensor [N, h, row_bytes] as
+        run_change_mask_device writes it for a region `width` pixels wide;
+        counts_out [N], boxes_out [N, K, 8] and links_out [N, K, 4] 4-byte
+        device tensors, every element of them written; prev (None: none) a
+        uint8 device tensor [h, row_bytes], the frame before the mask's
+        first; state (None: no carry) a 4-byte device tensor [1 + 2K], read
+        and written in the stream.  All 4-byte aligned."""
+        import torch
+        rw = int(width)
+        if mask.dim() != 3 or rw < 0 or mask.shape[2] != 4 * ((rw + 31) // 32) or mask.dtype != torch.uint8:
+            raise ValueError("mask must be a uint8 tensor of shape [N, h, 4 * ceil(width / 32)]")
+        n, rh = int(mask.shape[0]), int(mask.shape[1])
+        if boxes_out.dim() != 3 or boxes_out.shape[0] != n or boxes_out.shape[2] != _lib.BOX_WORDS:
+            raise ValueError("boxes_out must be a 4-byte tensor of shape [N, K, 8]")
+        conn, area, k, chunk = _tracks_args(connectivity, min_area, int(boxes_out.shape[1]), chunk_frames, n)
+        if tuple(counts_out.shape) != (n,):
+            raise ValueError("counts_out must be a 4-byte tensor of shape [N]")
+        if tuple(links_out.shape) != (n, k, _lib.LINK_WORDS):
+            raise ValueError("links_out must be a 4-byte tensor of shape [N, K, 4]")
+        if prev is not None:
+            if state is None:
+                raise ValueError("prev needs state")
+            if tuple(prev.shape) != tuple(mask.shape[1:]) or prev.dtype != torch.uint8:
+                raise ValueError("prev must be a uint8 tensor of shape [h, 4 * ceil(width / 32)]")
+        if state is not None and tuple(state.shape) != (1 + 2 * k,):
+            raise ValueError("state must be a 4-byte tensor of shape [1 + 2 * K]")
+        for t in (counts_out, boxes_out, links_out, state):
+            if t is not None and t.element_size() != 4:
+                raise ValueError("counts_out, boxes_out, links_out and state must be 4-byte tensors")
+        for t in (mask, prev, state, counts_out, boxes_out, links_out):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_tracks(
+                self._dev.ptr, mask.data_ptr() if mask.numel() else None, n, rw, rh, conn, area, k, chunk,
+                prev.data_ptr() if prev is not None and prev.numel() else None,
+                state.data_ptr() if state is not None else None,
+                counts_out.data_ptr() if n else None, boxes_out.data_ptr() if n else None,
+                links_out.data_ptr() if n else None))
+
     # -- the binary morphology of a change mask (dips_mask_morph) -------------
     def mask_morph(self, mask: ChangeMask, op, rx: int = 1, ry: Optional[int] = None,
                    shape=MorphShape.Box) -> ChangeMask:
@@ -1115,16 +1260,10 @@ class DiffSeriesOperator:
                 self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, op, shape, rx, ry,
                 out.data_ptr() if n else None))
 
-    def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
-                     max_boxes: int = 64, labels: bool = False, morph=None, background=None) -> ChangeBoxes:
-        """change_mask, then mask_components, with the mask kept on the
-        device between the two: the moving objects of every frame.  frames /
-        ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
-        sequence of (op, shape, rx, ry) steps of mask_morph applied in order
-        to the mask before its components are taken (None: none).
-        background: None, or rate_shift or (rate_shift, selective) to take
-        the mask against the running-average background (background_mask)
-        instead of the operator's mode."""
+    def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args):
+        """(mask, region width, region height, n): the change mask of
+        change_boxes / change_tracks as a device tensor, behind its morph
+        steps; check_args(n) runs once the geometry is known."""
         import torch
         dev = torch.device("cuda", self._dev.device)
 
@@ -1136,7 +1275,7 @@ class DiffSeriesOperator:
         frames, ref = on_device(frames), on_device(ref)
         n, h, w = _frame_geometry(frames, self.fmt)
         rh, rw = self._region(roi, h, w)
-        _, _, k, _ = _components_args(connectivity, min_area, max_boxes, 0, n)
+        check_args(n)
         steps = _morph_steps(morph, rw, rh) if morph is not None else []
         if background is not None:
             bg_k, bg_sel = background if isinstance(background, (tuple, list)) else (background, False)
@@ -1146,9 +1285,6 @@ class DiffSeriesOperator:
         if ref is not None:
             ref = ref.reshape(-1)
         mask = torch.empty((n, rh, 4 * ((rw + 31) // 32)), dtype=torch.uint8, device=dev)
-        counts = torch.empty((n,), dtype=torch.int32, device=dev)
-        boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
-        lab = torch.empty((n, rh, rw), dtype=torch.int32, device=dev) if labels else None
         if background is None:
             self.run_change_mask_device(frames, mask, roi=roi, ref=ref)
         else:
@@ -1159,12 +1295,55 @@ class DiffSeriesOperator:
             for op_, shape_, rx_, ry_ in steps:  # ping-pong: the newest mask is `mask`
                 self.run_mask_morph_device(mask, rw, other, op_, rx_, ry_, shape_)
                 mask, other = other, mask
+        return mask, rw, rh, n
+
+    def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
+                     max_boxes: int = 64, labels: bool = False, morph=None, background=None) -> ChangeBoxes:
+        """change_mask, then mask_components, with the mask kept on the
+        device between the two: the moving objects of every frame.  frames /
+        ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
+        sequence of (op, shape, rx, ry) steps of mask_morph applied in order
+        to the mask before its components are taken (None: none).
+        background: None, or rate_shift or (rate_shift, selective) to take
+        the mask against the running-average background (background_mask)
+        instead of the operator's mode."""
+        import torch
+        mask, rw, rh, n = self._change_mask_on_device(
+            frames, roi, ref, morph, background,
+            lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_))
+        dev, k = mask.device, int(max_boxes)
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
+        lab = torch.empty((n, rh, rw), dtype=torch.int32, device=dev) if labels else None
         self.run_mask_components_device(mask, rw, counts, boxes, lab, connectivity=connectivity, min_area=min_area)
 
         def to_u32(t):
             return t.cpu().numpy().view(np.uint32)  # the copy waits for the stream
 
         return ChangeBoxes(to_u32(counts), to_u32(boxes), to_u32(lab) if lab is not None else None)
+
+    def change_tracks(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
+                      max_boxes: int = 64, morph=None, background=None) -> ChangeTracks:
+        """change_mask, then mask_tracks, with the mask kept on the device
+        between the two: the moving objects of every frame and their
+        identity from frame to frame.  The arguments are change_boxes'; the
+        state of the result continues the ids in a later mask_tracks call."""
+        import torch
+        mask, rw, rh, n = self._change_mask_on_device(
+            frames, roi, ref, morph, background,
+            lambda n_: _tracks_args(connectivity, min_area, max_boxes, 0, n_))
+        dev, k = mask.device, int(max_boxes)
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
+        links = torch.empty((n, k, _lib.LINK_WORDS), dtype=torch.int32, device=dev)
+        state = torch.zeros((1 + 2 * k,), dtype=torch.int32, device=dev)
+        self.run_mask_tracks_device(mask, rw, counts, boxes, links, state=state, connectivity=connectivity,
+                                    min_area=min_area)
+
+        def to_u32(t):
+            return t.cpu().numpy().view(np.uint32)  # the copy waits for the stream
+
+        return ChangeTracks(to_u32(counts), to_u32(boxes), to_u32(links), to_u32(state))
 
     # -- the change times per pixel (dips_diff_pixel_times) --------------------
     def pixel_times(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None, t0: int = 0,
@@ -1372,7 +1551,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "Background", "mask_row_bytes", "grid_cell",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "ChangeTracks", "Background", "mask_row_bytes", "grid_cell",
     "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",

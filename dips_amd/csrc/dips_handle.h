@@ -42,7 +42,8 @@ struct dips_handle {
     dips_host::DevBuf partials, stage_frames, stage_ref, stage_series, stage_map;
     dips_host::DevBuf probe_out;  // sink of the read-ceiling kernels
     dips_host::DevBuf times_parts;  // per-part summaries of dips_diff_pixel_times (series_times.hip)
-    dips_host::DevBuf cc_scratch;   // union-find and statistics of dips_mask_components (mask_components.hip)
+    dips_host::DevBuf cc_scratch;   // union-find and statistics of dips_mask_components (mask_components.hip),
+                                    // the overlap tables and the carry of dips_mask_tracks (mask_tracks.hip)
     std::map<const void*, int> occupancy;
 
     // streamed feed

@@ -369,6 +369,37 @@ struct ComponentsArgs {
     uint32_t max_boxes;
 };
 
+// The links of a chunk of labelled mask frames to their predecessors
+// (mask_tracks.hip).  `parent` and `label` are the planes
+// launch_mask_components left, with one more plane in front: plane f + 1 is
+// the chunk's frame f and plane f its predecessor, so plane 0 is the frame
+// before the chunk.
+struct TracksArgs {
+    const uint32_t* mask;      // the chunk's frames, h * wpr words each
+    const uint32_t* prev0;     // the frame before the chunk in the same layout; NULL: frame 0 has no predecessor
+    uint32_t* parent;          // (n_frames + 1) * npx: every node's root
+    uint32_t* label;           // (n_frames + 1) * nslots: ComponentsArgs::area after cc_select_kernel
+    const uint32_t* counts;    // the chunk's part of the output, already written
+    uint32_t* ov;              // n_frames * K * K, zero on entry: ov[f][a][b]
+    uint32_t* cprev;           // n_frames * K: the record continued, DIPS_LINK_NONE for a head or no record
+    uint32_t* hrank;           // n_frames * K: a head's rank among the heads of its frame
+    uint32_t* heads;           // n_frames: heads per frame
+    uint32_t* base;            // n_frames: the id of the frame's first head
+    uint32_t* next_id;         // one word: the next unused id, read and advanced
+    const uint32_t* carry_in;  // 2 * K: TRACK, then AGE, of the records of the frame before the chunk
+    uint32_t* carry_out;       // 2 * K: the same of the chunk's last frame (not carry_in)
+    uint32_t* links;           // the chunk's part of the output
+    uint32_t w, h;
+    uint32_t npx;              // w * h < 2^30
+    uint32_t wpr;              // mask words per row
+    uint32_t hw;               // slots per row, ceil(w / 2)
+    uint32_t nslots;           // hw * h
+    uint32_t wpf;              // mask words per frame
+    uint32_t bpf;              // blocks of 256 words per frame
+    uint32_t n_frames;         // of the chunk
+    uint32_t K;                // max_boxes, 1 .. DIPS_TRACK_MAX_BOXES
+};
+
 // The binary morphology of a batch of change-mask frames (mask_morph.hip):
 // one launch, tiles of the frames as a flattened 64-bit index.
 struct MorphArgs {
@@ -595,6 +626,14 @@ hipError_t launch_background_generic(const BgGenericArgs& a, int channels, hipSt
 // the connected components of a chunk of mask frames (mask_components.hip):
 // every launch of the chunk, in order, on `s`
 hipError_t launch_mask_components(const ComponentsArgs& a, hipStream_t s);
+// the links of a chunk of frames labelled by launch_mask_components on the
+// same stream (mask_tracks.hip): the clear of the overlap table and the four
+// launches, in order, on `s`
+hipError_t launch_mask_tracks(const TracksArgs& a, hipStream_t s);
+// plane `plane` of parent and label, the labelling of the frame at `frame`,
+// becomes plane 0, the predecessor of the next chunk: one launch over the
+// frame's words that copies what its runs own and nothing else
+hipError_t launch_mask_tracks_keep(const TracksArgs& a, const uint32_t* frame, uint32_t plane, hipStream_t s);
 // the binary morphology of mask frames (mask_morph.hip): the one launch of a
 // call on `s`, and the tiles it cuts a w x h frame into
 hipError_t launch_mask_morph(const MorphArgs& a, hipStream_t s);

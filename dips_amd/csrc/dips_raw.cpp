@@ -45,14 +45,20 @@
 //            anchor,cx256,cy256, one row per stored record, and a line
 //            "# frame,count" per frame (count is not capped by K); stdout one
 //            line with the region, the frames, the components and the records
+//            [--tracks FILE [--connectivity 4|8] [--min-area A] [--max-boxes K]
+//            [--roi x,y,w,h]] -> the same components linked across frames with
+//            dips_mask_tracks (K 1 .. 256): FILE is --boxes' file with the
+//            columns prev,overlap,track,age behind every record (4294967295:
+//            none); the stdout line begins with "tracks" and ends with
+//            tracks=<ids handed out>
 //            [--morph erode|dilate|open|close:box|diamond:RXxRY]... -> with
-//            --mask or --boxes: the binary morphology of the change mask with
+//            --mask, --boxes or --tracks: the binary morphology of the change mask with
 //            dips_mask_morph (radii 0 .. 15, a diamond needs RX = RY), the steps
 //            applied in the order given; --mask then writes the cleaned mask
-//            and --boxes takes the components of the cleaned mask, and the
+//            and --boxes / --tracks take the components of the cleaned mask, and the
 //            stdout line ends with morph=<steps>
 //            [--background K[,selective] [--background-out FILE]] -> with
-//            --mask or --boxes: the mask is taken against the running-average
+//            --mask, --boxes or --tracks: the mask is taken against the running-average
 //            background with dips_diff_background_mask (rate_shift K in
 //            0 .. 8, starting at frame 0) instead of --mode's reference;
 //            --background-out gets the final state, channel planes of roi_h x
@@ -124,8 +130,9 @@ int usage() {
                  "                [--chunk N] [--grid RxC [--roi x,y,w,h]] [--pixel-sums FILE [--roi x,y,w,h]]\n"
                  "                [--mask FILE [--roi x,y,w,h]] [--pixel-times FILE [--roi x,y,w,h]]\n"
                  "                [--boxes FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
-                 "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask or --boxes)\n"
-                 "                [--background K[,selective] [--background-out FILE]] (with --mask or --boxes)\n"
+                 "                [--tracks FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
+                 "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask, --boxes or --tracks)\n"
+                 "                [--background K[,selective] [--background-out FILE]] (with --mask, --boxes or --tracks)\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -513,6 +520,7 @@ int run_series(int argc, char** argv) {
     const char* mask_path = nullptr;
     const char* times_path = nullptr;
     const char* boxes_path = nullptr;
+    const char* tracks_path = nullptr;
     uint32_t connectivity = 8, min_area = 1, max_boxes = 64;
     bool has_box_opt = false;
     std::vector<MorphStep> morph;
@@ -544,6 +552,8 @@ int run_series(int argc, char** argv) {
             times_path = argv[++i];
         } else if (a == "--boxes" && has) {
             boxes_path = argv[++i];
+        } else if (a == "--tracks" && has) {
+            tracks_path = argv[++i];
         } else if ((a == "--connectivity" || a == "--min-area" || a == "--max-boxes") && has) {
             uint32_t* v = a == "--connectivity" ? &connectivity : a == "--min-area" ? &min_area : &max_boxes;
             if (!parse_u32_or_zero(argv[++i], v)) return usage();
@@ -563,16 +573,16 @@ int run_series(int argc, char** argv) {
             return usage();
         }
     }
-    // --morph belongs to --mask or --boxes
-    if (!morph.empty() && !mask_path && !boxes_path) return usage();
-    // --background belongs to --mask or --boxes, --background-out to --background
-    if ((bg.on && !mask_path && !boxes_path) || (bg.out_path && !bg.on)) return usage();
-    // --roi belongs to --grid, --pixel-sums, --mask, --pixel-times or --boxes
-    if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path && !boxes_path) return usage();
+    // --morph belongs to --mask, --boxes or --tracks
+    if (!morph.empty() && !mask_path && !boxes_path && !tracks_path) return usage();
+    // --background belongs to --mask, --boxes or --tracks, --background-out to --background
+    if ((bg.on && !mask_path && !boxes_path && !tracks_path) || (bg.out_path && !bg.on)) return usage();
+    // --roi belongs to --grid, --pixel-sums, --mask, --pixel-times, --boxes or --tracks
+    if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path && !boxes_path && !tracks_path) return usage();
     if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) +
-            (boxes_path != nullptr) > 1)
+            (boxes_path != nullptr) + (tracks_path != nullptr) > 1)
         return usage();
-    if (has_box_opt && !boxes_path) return usage();
+    if (has_box_opt && !boxes_path && !tracks_path) return usage();
     if (connectivity != 4u && connectivity != 8u) return usage();
     Mapped in;
     if (!in.open(argv[2])) {
@@ -676,15 +686,21 @@ int run_series(int argc, char** argv) {
         std::printf("\n");
         return 0;
     }
-    if (boxes_path) {
+    if (boxes_path || tracks_path) {
+        // --tracks: the same file with the four link words behind every record
+        const bool tracks = tracks_path != nullptr;
+        const char* out_path = tracks ? tracks_path : boxes_path;
         const uint32_t rw = has_roi ? roi[2] : w, rh = has_roi ? roi[3] : h;
         // a region or a record count the library will refuse gets one element: nothing is written to it
         uint32_t rect[4];
         const bool sane = dips_grid_cell(w, h, has_roi ? roi : nullptr, 1u, 1u, 0u, 0u, rect) == DIPS_OK &&
                           (uint64_t)rw * rh < (1ull << 30) && rw < (1u << 24) && rh < (1u << 24) &&
-                          (uint64_t)n * max_boxes * DIPS_BOX_WORDS < (1ull << 32);
+                          (uint64_t)n * max_boxes * DIPS_BOX_WORDS < (1ull << 32) &&
+                          (!tracks || max_boxes <= DIPS_TRACK_MAX_BOXES);
         std::vector<uint8_t> mask(sane ? (size_t)n * rh * dips_mask_row_bytes(rw) : 1u);
         std::vector<uint32_t> counts(sane ? (size_t)n : 1u), recs(sane ? (size_t)n * max_boxes * DIPS_BOX_WORDS : 1u);
+        std::vector<uint32_t> links(sane && tracks ? (size_t)n * max_boxes * DIPS_LINK_WORDS : 1u);
+        std::vector<uint32_t> ids(sane && tracks ? 1u + 2u * (size_t)max_boxes : 1u);  // the state: [0] counts the tracks
         std::vector<uint16_t> state(sane && bg.on ? (size_t)p.format * rw * rh : 1u);
         const char* what = nullptr;
         st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, state, mask.data(), &what);
@@ -692,7 +708,11 @@ int run_series(int argc, char** argv) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
         }
-        if (st == DIPS_OK) {
+        if (st == DIPS_OK && tracks) {
+            what = "dips_mask_tracks";
+            st = dips_mask_tracks(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, nullptr, ids.data(),
+                                  counts.data(), recs.data(), links.data());
+        } else if (st == DIPS_OK) {
             what = "dips_mask_components";
             st = dips_mask_components(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, counts.data(),
                                       max_boxes ? recs.data() : nullptr, nullptr);
@@ -704,29 +724,36 @@ int run_series(int argc, char** argv) {
         }
         dips_destroy(hd);
         if (write_background(bg, state) != 0) return 1;
-        std::FILE* f = std::fopen(boxes_path, "w");
+        std::FILE* f = std::fopen(out_path, "w");
         if (!f) {
-            std::fprintf(stderr, "dips_raw: cannot write %s\n", boxes_path);
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", out_path);
             return 1;
         }
-        std::fprintf(f, "frame,k,x0,y0,x1,y1,area,anchor,cx256,cy256\n");
+        std::fprintf(f, "frame,k,x0,y0,x1,y1,area,anchor,cx256,cy256%s\n", tracks ? ",prev,overlap,track,age" : "");
         unsigned long long total = 0, stored = 0;
         for (uint32_t t = 0; t < n; ++t) {
             std::fprintf(f, "# %u,%u\n", t, counts[t]);
             total += counts[t];
             for (uint32_t k = 0; k < std::min(counts[t], max_boxes); ++k, ++stored) {
                 const uint32_t* r = &recs[((size_t)t * max_boxes + k) * DIPS_BOX_WORDS];
-                std::fprintf(f, "%u,%u,%u,%u,%u,%u,%u,%u,%u,%u\n", t, k, r[DIPS_BOX_X0], r[DIPS_BOX_Y0], r[DIPS_BOX_X1],
+                std::fprintf(f, "%u,%u,%u,%u,%u,%u,%u,%u,%u,%u", t, k, r[DIPS_BOX_X0], r[DIPS_BOX_Y0], r[DIPS_BOX_X1],
                              r[DIPS_BOX_Y1], r[DIPS_BOX_AREA], r[DIPS_BOX_ANCHOR], r[DIPS_BOX_CX256], r[DIPS_BOX_CY256]);
+                if (tracks) {
+                    const uint32_t* l = &links[((size_t)t * max_boxes + k) * DIPS_LINK_WORDS];
+                    std::fprintf(f, ",%u,%u,%u,%u", l[DIPS_LINK_PREV], l[DIPS_LINK_OVERLAP], l[DIPS_LINK_TRACK],
+                                 l[DIPS_LINK_AGE]);
+                }
+                std::fprintf(f, "\n");
             }
         }
         if (std::ferror(f) != 0 || std::fclose(f) != 0) {
-            std::fprintf(stderr, "dips_raw: cannot write %s\n", boxes_path);
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", out_path);
             return 1;
         }
-        std::printf("boxes roi=%u,%u,%u,%u frames=%u connectivity=%u min_area=%u max_boxes=%u components=%llu records=%llu",
-                    has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, connectivity, min_area, max_boxes, total,
-                    stored);
+        std::printf("%s roi=%u,%u,%u,%u frames=%u connectivity=%u min_area=%u max_boxes=%u components=%llu records=%llu",
+                    tracks ? "tracks" : "boxes", has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, connectivity,
+                    min_area, max_boxes, total, stored);
+        if (tracks) std::printf(" tracks=%u", ids[0]);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
         print_background(bg);
         std::printf("\n");

@@ -54,6 +54,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dips_kernels.h"
+#include "mask_runs.h"  // next_run, local_start
 
 namespace dips {
 
@@ -91,20 +92,6 @@ __device__ __forceinline__ uint32_t mask_word(const ComponentsArgs& a, uint32_t 
     uint32_t v = a.mask[((size_t)f * a.h + j) * a.wpr + k];
     if (k == a.wpr - 1u && (a.w & 31u) != 0u) v &= (1u << (a.w & 31u)) - 1u;
     return v;
-}
-
-// The first run of `rem` (non-zero): bits [s, e); `rem` loses them.
-__device__ __forceinline__ void next_run(uint32_t& rem, uint32_t& s, uint32_t& e) {
-    s = (uint32_t)__ffs((int)rem) - 1u;
-    const uint32_t clear = ~rem & (~0u << s);
-    e = clear ? (uint32_t)__ffs((int)clear) - 1u : 32u;
-    rem = e < 32u ? rem & (~0u << e) : 0u;
-}
-
-// Start of the word-local run of `word` that holds set bit b.
-__device__ __forceinline__ uint32_t local_start(uint32_t word, uint32_t b) {
-    const uint32_t below = ~word & ((1u << b) - 1u);
-    return below ? 32u - (uint32_t)__clz((int)below) : 0u;
 }
 
 __device__ __forceinline__ uint32_t find_root(const uint32_t* parent, uint32_t x) {

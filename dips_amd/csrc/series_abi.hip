@@ -1217,6 +1217,145 @@ dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t 
 }
 
 // ---------------------------------------------------------------------------
+// The components of a mask linked across frames (dips_mask_tracks; kernels in
+// mask_components.hip and mask_tracks.hip)
+// ---------------------------------------------------------------------------
+
+// tr_ids_kernel walks a chain back to the chunk's first frame at most: the
+// cap keeps that walk, one dependent load per frame, short whatever the clip
+constexpr uint32_t kTracksChunkFrames = 256;
+
+// Label and link the frames of a device mask, asynchronously on `s`, `chunk`
+// frames per round (0: automatic) in the handle's scratch.  The parent and
+// label planes have one more frame in front, the predecessor of the chunk's
+// first frame: prev_mask is labelled into it, and what the runs of a chunk's
+// last frame own is copied there for the next chunk.  The next id and the last frame's tracks
+// and ages stay in the scratch from chunk to chunk (two buffers, swapped) and
+// move from and to `state` by copies in the stream.
+dips_status run_tracks_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                              uint32_t connectivity, uint32_t min_area, uint32_t K, uint32_t chunk,
+                              const uint8_t* prev_mask, uint32_t* state, uint32_t* counts, uint32_t* boxes,
+                              uint32_t* links, hipStream_t s) {
+    dips::ComponentsArgs a{};
+    a.w = w;
+    a.h = hgt;
+    a.npx = w * hgt;
+    a.wpr = (uint32_t)mask_words_per_row(w);
+    a.hw = (w + 1u) / 2u;
+    a.nslots = a.hw * hgt;
+    a.wpf = a.wpr * hgt;
+    a.bpf = (a.wpf + 255u) / 256u;
+    a.connectivity = connectivity;
+    a.min_area = min_area;
+    // per frame: the labelling's share, the overlap table, cprev and hrank, heads and base;
+    // once: the plane in front of parent and of the labels, next id, a count, two carries
+    const size_t per_frame =
+        4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf + 4u * (size_t)K * K + 8u * (size_t)K + 8u;
+    const size_t fixed = 4u * (size_t)a.npx + 4u * (size_t)a.nslots + 16u * (size_t)K + 8u;
+    uint64_t frames =
+        chunk ? chunk
+              : std::max<uint64_t>(1u, (kComponentsScratchBytes - std::min(fixed, kComponentsScratchBytes)) / per_frame);
+    frames = std::min<uint64_t>(frames, n_frames);
+    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
+    frames = std::min<uint64_t>(frames, kTracksChunkFrames);
+    const uint32_t F = (uint32_t)frames;
+    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F + fixed));
+    uint8_t* base = h->cc_scratch.as<uint8_t>();
+    a.sum_i = reinterpret_cast<uint64_t*>(base);
+    a.sum_j = a.sum_i + (size_t)F * a.nslots;
+    uint32_t* label0 = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);  // F + 1 planes
+    a.area = label0 + a.nslots;
+    a.min_x = a.area + (size_t)F * a.nslots;
+    a.max_x = a.min_x + (size_t)F * a.nslots;
+    a.max_y = a.max_x + (size_t)F * a.nslots;
+    uint32_t* parent0 = a.max_y + (size_t)F * a.nslots;  // F + 1 planes
+    a.parent = parent0 + a.npx;
+    a.block_count = a.parent + (size_t)F * a.npx;
+
+    dips::TracksArgs tr{};
+    tr.parent = parent0;
+    tr.label = label0;
+    tr.ov = a.block_count + (size_t)F * a.bpf;
+    tr.cprev = tr.ov + (size_t)F * K * K;
+    tr.hrank = tr.cprev + (size_t)F * K;
+    tr.heads = tr.hrank + (size_t)F * K;
+    tr.base = tr.heads + F;
+    tr.next_id = tr.base + F;
+    uint32_t* prev_count = tr.next_id + 1;
+    uint32_t* carry[2] = {prev_count + 1, prev_count + 1 + 2u * (size_t)K};
+    tr.w = a.w;
+    tr.h = a.h;
+    tr.npx = a.npx;
+    tr.wpr = a.wpr;
+    tr.hw = a.hw;
+    tr.nslots = a.nslots;
+    tr.wpf = a.wpf;
+    tr.bpf = a.bpf;
+    tr.K = K;
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    const size_t frame_words = (size_t)a.wpf;
+    if (state)
+        DIPS_HIP(h, hipMemcpyAsync(tr.next_id, state, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    else
+        DIPS_HIP(h, hipMemsetAsync(tr.next_id, 0, sizeof(uint32_t), s));
+    if (prev_mask) {
+        DIPS_HIP(h, hipMemcpyAsync(carry[0], state + 1, sizeof(uint32_t) * 2u * K, hipMemcpyDeviceToDevice, s));
+        // the same labels as the call that held this frame gave it: they do not depend on max_boxes
+        a.n_frames = 1;
+        a.mask = reinterpret_cast<const uint32_t*>(prev_mask);
+        a.counts = prev_count;
+        a.boxes = nullptr;
+        a.max_boxes = 0;
+        DIPS_HIP(h, dips::launch_mask_components(a, s));
+        DIPS_HIP(h, dips::launch_mask_tracks_keep(tr, a.mask, 1u, s));
+    }
+    a.max_boxes = K;
+    // the records no component fills are zeros
+    DIPS_HIP(h, hipMemsetAsync(boxes, 0, sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * K, s));
+    tr.prev0 = reinterpret_cast<const uint32_t*>(prev_mask);
+    uint32_t cin = 0;
+    for (uint32_t t = 0; t < n_frames; t += F) {
+        const uint32_t n = std::min(F, n_frames - t);
+        a.n_frames = n;
+        a.mask = reinterpret_cast<const uint32_t*>(mask) + (size_t)t * frame_words;
+        a.counts = counts + t;
+        a.boxes = boxes + (size_t)t * K * DIPS_BOX_WORDS;
+        DIPS_HIP(h, dips::launch_mask_components(a, s));
+        tr.n_frames = n;
+        tr.mask = a.mask;
+        tr.counts = a.counts;
+        tr.links = links + (size_t)t * K * DIPS_LINK_WORDS;
+        tr.carry_in = carry[cin];
+        tr.carry_out = carry[cin ^ 1u];
+        DIPS_HIP(h, dips::launch_mask_tracks(tr, s));
+        cin ^= 1u;
+        if (t + n < n_frames) {
+            tr.prev0 = a.mask + (size_t)(n - 1u) * frame_words;
+            DIPS_HIP(h, dips::launch_mask_tracks_keep(tr, tr.prev0, n, s));
+        }
+    }
+    if (state) {
+        DIPS_HIP(h, hipMemcpyAsync(state, tr.next_id, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        DIPS_HIP(h, hipMemcpyAsync(state + 1, carry[cin], sizeof(uint32_t) * 2u * K, hipMemcpyDeviceToDevice, s));
+    }
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    return DIPS_OK;
+}
+
+// ---------------------------------------------------------------------------
 // The binary morphology of a mask (dips_mask_morph; kernel in mask_morph.hip)
 // ---------------------------------------------------------------------------
 
@@ -1666,6 +1805,66 @@ dips_status dips_mask_components(dips_handle* h, const uint8_t* mask, uint32_t n
         if (max_boxes != 0u)
             DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
         if (labels) DIPS_HIP(h, hipMemcpyAsync(labels, h->stage_map.p, labels_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_tracks(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                             uint32_t connectivity, uint32_t min_area, uint32_t max_boxes, uint32_t chunk_frames,
+                             const uint8_t* prev_mask, uint32_t* state, uint32_t* counts, uint32_t* boxes,
+                             uint32_t* links) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask || !counts || !boxes || !links) return fail(h, DIPS_ERR_INVALID, "mask_tracks: null argument");
+        if (max_boxes == 0u || max_boxes > DIPS_TRACK_MAX_BOXES)
+            return fail(h, DIPS_ERR_INVALID, "mask_tracks: max_boxes must be 1 .. 256");
+        if (prev_mask && !state) return fail(h, DIPS_ERR_INVALID, "mask_tracks: prev_mask needs state");
+        if (connectivity != 4u && connectivity != 8u)
+            return fail(h, DIPS_ERR_INVALID, "mask_tracks: connectivity must be 4 or 8");
+        if (roi_w == 0 || roi_h == 0 || roi_w >= (1u << 24) || roi_h >= (1u << 24))
+            return fail(h, DIPS_ERR_INVALID, "mask_tracks: roi_w and roi_h must be 1 .. 2^24 - 1");
+        const uint64_t n_px = (uint64_t)roi_w * roi_h;
+        if (n_px >= (1ull << 30)) return fail(h, DIPS_ERR_INVALID, "mask_tracks: the region must stay below 2^30 pixels");
+        if ((uint64_t)n_frames * max_boxes * DIPS_BOX_WORDS >= (1ull << 32))
+            return fail(h, DIPS_ERR_INVALID, "mask_tracks: n_frames * max_boxes * 8 must stay below 2^32");
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            if ((((uintptr_t)mask | (uintptr_t)prev_mask | (uintptr_t)state | (uintptr_t)counts | (uintptr_t)boxes |
+                  (uintptr_t)links) & 3u) != 0)
+                return fail(h, DIPS_ERR_INVALID, "mask_tracks: the device pointers must be 4-byte aligned");
+            return run_tracks_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes, chunk_frames,
+                                     prev_mask, state, counts, boxes, links, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call); the frame
+        // before the clip behind the mask, the outputs and the state in one buffer
+        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        const size_t mask_bytes = frame_bytes * n_frames;
+        const size_t counts_words = (size_t)n_frames;
+        const size_t boxes_words = DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
+        const size_t links_words = DIPS_LINK_WORDS * (size_t)n_frames * max_boxes;
+        const size_t state_words = 1u + 2u * (size_t)max_boxes;
+        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes + frame_bytes));
+        DIPS_HIP(h, h->stage_series.ensure(sizeof(uint32_t) * (counts_words + boxes_words + links_words + state_words)));
+        uint8_t* mask_dev = h->stage_frames.as<uint8_t>();
+        uint8_t* prev_dev = prev_mask ? mask_dev + mask_bytes : nullptr;
+        uint32_t* counts_dev = h->stage_series.as<uint32_t>();
+        uint32_t* boxes_dev = counts_dev + counts_words;
+        uint32_t* links_dev = boxes_dev + boxes_words;
+        uint32_t* state_dev = state ? links_dev + links_words : nullptr;
+        DIPS_HIP(h, hipMemcpyAsync(mask_dev, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        if (prev_mask) DIPS_HIP(h, hipMemcpyAsync(prev_dev, prev_mask, frame_bytes, hipMemcpyHostToDevice, h->stream));
+        if (state)
+            DIPS_HIP(h, hipMemcpyAsync(state_dev, state, sizeof(uint32_t) * state_words, hipMemcpyHostToDevice, h->stream));
+        st = run_tracks_device(h, mask_dev, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes, chunk_frames,
+                               prev_dev, state_dev, counts_dev, boxes_dev, links_dev, h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, sizeof(uint32_t) * counts_words, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, sizeof(uint32_t) * boxes_words, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipMemcpyAsync(links, links_dev, sizeof(uint32_t) * links_words, hipMemcpyDeviceToHost, h->stream));
+        if (state)
+            DIPS_HIP(h, hipMemcpyAsync(state, state_dev, sizeof(uint32_t) * state_words, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

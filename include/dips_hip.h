@@ -489,6 +489,77 @@ dips_status dips_mask_components(dips_handle *h, const uint8_t *mask, uint32_t n
                                  uint32_t chunk_frames,
                                  uint32_t *counts, uint32_t *boxes, uint32_t *labels);
 
+/* The components of a change mask linked across frames: tracks.  The step
+ * from "boxes per frame" to the identity of a moving object, how long it has
+ * been visible, where it came from when one blob splits and where it went
+ * when two merge (difference -> threshold -> morphology -> components ->
+ * tracks).  The reference has no counterpart.  It reads masks only, so it
+ * serves every pixel format and both mask sources, and it is exact.
+ * mask, roi_w, roi_h, connectivity, min_area, max_boxes (K), chunk_frames,
+ * counts and boxes mean exactly what they mean in dips_mask_components, and
+ * counts and boxes of this call equal that call's, word for word, on the same
+ * arguments.  The records of frame t are its first m_t = min(counts[t], K)
+ * kept components.  K must be 1 .. DIPS_TRACK_MAX_BOXES: the link stage keeps
+ * a K x K overlap table per frame.
+ * Overlap: for record a of frame t and record b of frame t - 1, ov(t, a, b)
+ * is the number of pixels (j, i) that lie in component a in frame t and in
+ * component b in frame t - 1.  Components beyond K and components dropped by
+ * min_area take no part.  Frame -1 is prev_mask (one frame in the mask
+ * layout, pad bits ignored), labelled with the same arguments; if prev_mask
+ * is NULL, frame 0 has no predecessor and all its ov are 0.
+ * links[(t*K + k)*DIPS_LINK_WORDS + f], for k < m_t:
+ *   PREV     the b with the largest ov(t, k, b) > 0, the smallest such b on a
+ *            tie, DIPS_LINK_NONE if every ov is 0;
+ *   OVERLAP  that ov (0 with NONE);
+ *   TRACK, AGE  with NEXT(t - 1, b) the a with the largest ov(t, a, b) > 0,
+ *            the smallest a on a tie: record k continues b when PREV = b and
+ *            NEXT(t - 1, b) = k, a mutual best match.  Then TRACK = TRACK of
+ *            (t - 1, b) and AGE = its AGE + 1.  Otherwise the record is a
+ *            head: AGE = 0 and TRACK is the next unused id.  Ids are handed
+ *            out to heads in ascending (t, k) order, starting at state[0] (0
+ *            when state is NULL); arithmetic on ids and ages is modulo 2^32.
+ * For k >= m_t the record is {NONE, 0, NONE, 0}.  Every word of links is
+ * written.  Consequences: a blob that splits keeps its track in the child
+ * that shares the most pixels with it, and the other child is a head whose
+ * PREV still names the parent; of two blobs that merge, the one contributing
+ * more pixels continues; an object that vanishes for a frame returns under a
+ * new id.
+ * state (NULL: no carry) is 1 + 2K words, read before and written after:
+ * [0] the next unused id, [1 + k] TRACK of record k of the predecessor frame,
+ * [1 + K + k] its AGE ({NONE, 0} for k beyond its records).  On return it
+ * describes the call's last frame; it is unchanged when n_frames = 0.  It is
+ * read for tracks and ages only when prev_mask is given, and prev_mask
+ * without state is DIPS_ERR_INVALID.  A clip of any length goes call by call:
+ * pass the previous call's last mask frame as prev_mask and the same state
+ * buffer, and the result equals the one call over the whole clip, bit for
+ * bit.  roi_w, roi_h, connectivity, min_area and max_boxes must be the same
+ * from call to call: prev_mask is labelled with this call's, and state is
+ * indexed by its records.  state given without prev_mask is a scene cut: the
+ * ids go on, every record of frame 0 is a head.
+ * chunk_frames, DIPS_FLAG_TIME_KERNEL and n_frames == 0 as in
+ * dips_mask_components; the scratch of a round includes its overlap tables,
+ * and a round holds at most 256 frames.
+ * DIPS_FLAG_DEVICE_PTRS: all six pointers are device pointers, 4-byte
+ * aligned, the call asynchronous on the handle's stream with no host
+ * synchronisation (the carried id stays on the device); else host pointers of
+ * any alignment, staged through HBM, synchronous.  DIPS_ERR_INVALID, outputs
+ * untouched: that call's cases, and K = 0 or K > DIPS_TRACK_MAX_BOXES, null
+ * boxes or links, prev_mask without state.  DIPS_ERR_NOMEM if the scratch
+ * cannot be allocated. */
+#define DIPS_LINK_PREV 0u
+#define DIPS_LINK_OVERLAP 1u
+#define DIPS_LINK_TRACK 2u
+#define DIPS_LINK_AGE 3u
+#define DIPS_LINK_WORDS 4u
+#define DIPS_LINK_NONE 0xFFFFFFFFu
+#define DIPS_TRACK_MAX_BOXES 256u
+dips_status dips_mask_tracks(dips_handle *h, const uint8_t *mask, uint32_t n_frames,
+                             uint32_t roi_w, uint32_t roi_h,
+                             uint32_t connectivity, uint32_t min_area, uint32_t max_boxes,
+                             uint32_t chunk_frames,
+                             const uint8_t *prev_mask, uint32_t *state,
+                             uint32_t *counts, uint32_t *boxes, uint32_t *links);
+
 /* The binary morphology of a change mask, frame by frame: the cleanup
  * between threshold and components (difference -> threshold -> morphology ->
  * components -> boxes).  The reference has no counterpart.  A second stage

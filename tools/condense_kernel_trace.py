@@ -16,7 +16,8 @@ import sys
 OURS = ("series_v2_kernel", "series_reduce_kernel", "series_pixels_kernel", "pixels_generic_kernel",
         "series_mask_kernel", "mask_generic_kernel", "series_times_kernel", "times_combine_kernel",
         "times_generic_kernel", "cc_rows_kernel", "cc_merge_kernel", "cc_stats_kernel", "cc_count_kernel",
-        "cc_offsets_kernel", "cc_select_kernel", "cc_labels_kernel", "series_background_kernel",
+        "cc_offsets_kernel", "cc_select_kernel", "cc_labels_kernel", "tr_overlap_kernel", "tr_link_kernel",
+        "tr_scan_kernel", "tr_ids_kernel", "tr_keep_kernel", "series_background_kernel",
         "background_generic_kernel")
 
 
