@@ -53,6 +53,9 @@ MORPH_BOX, MORPH_DIAMOND = 0, 1  # DIPS_MORPH_BOX, DIPS_MORPH_DIAMOND
 MORPH_MAX_RADIUS = 15  # DIPS_MORPH_MAX_RADIUS
 BG_SELECTIVE = 1  # DIPS_BG_SELECTIVE
 BG_MAX_RATE_SHIFT = 8  # DIPS_BG_MAX_RATE_SHIFT
+SD_MAX_AMP = 15  # DIPS_SD_MAX_AMP
+SD_MAX_V = 510  # DIPS_SD_MAX_V
+SD_PLANES = 2  # DIPS_SD_PLANES
 
 COMM_ID_BYTES = 128
 COMM_RCCL = 1
@@ -197,6 +200,7 @@ def load() -> ctypes.CDLL:
             "dips_diff_change_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), _u8p], st),
             "dips_diff_pixel_times": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, _vp], st),
             "dips_diff_background_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, u32, _vp, _u8p], st),
+            "dips_diff_sigma_delta_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, u32, u32, _vp, _u8p], st),
             "dips_mask_components": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _vp, _vp, _vp], st),
             "dips_mask_tracks": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, _vp, _vp, _vp, _vp], st),
             "dips_mask_morph": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p], st),

@@ -573,6 +573,54 @@ def _background_args(rate_shift, selective) -> Tuple[int, int]:
 
 
 @dataclass
+class SigmaDelta:
+    """The Sigma-Delta background of a region (dips_diff_sigma_delta_mask):
+    `state` uint16 [2, h, w], plane 0 the running median M of the integer
+    intensity J (0 .. 510), plane 1 the per-pixel threshold V."""
+    state: np.ndarray
+
+    @property
+    def median(self) -> np.ndarray:
+        """uint16 [h, w]: M, in units of J (twice an 8-bit intensity)."""
+        return self.state[0]
+
+    @property
+    def threshold(self) -> np.ndarray:
+        """uint16 [h, w]: V, the deviation of J a pixel must exceed to fire."""
+        return self.state[1]
+
+    @classmethod
+    def from_array(cls, a: np.ndarray) -> "SigmaDelta":
+        a = np.ascontiguousarray(a, dtype=np.uint16)
+        if a.ndim != 3 or a.shape[0] != _lib.SD_PLANES:
+            raise ValueError("Sigma-Delta state must be [2, h, w]")
+        return cls(a)
+
+
+def _sigma_delta_args(n_amp, v_min, v_max) -> Tuple[int, int, int]:
+    """n_amp, v_min and v_max of dips_diff_sigma_delta_mask, checked."""
+    for v in (n_amp, v_min, v_max):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("n_amp, v_min and v_max must be integers")
+    n_amp, v_min, v_max = int(n_amp), int(v_min), int(v_max)
+    if not 1 <= n_amp <= _lib.SD_MAX_AMP:
+        raise ValueError(f"n_amp must be 1 .. {_lib.SD_MAX_AMP}")
+    if not 0 <= v_min <= v_max <= _lib.SD_MAX_V:
+        raise ValueError(f"0 <= v_min <= v_max <= {_lib.SD_MAX_V} is required")
+    return n_amp, v_min, v_max
+
+
+def _sigma_delta_option(sigma_delta) -> Tuple[int, int, int]:
+    """The sigma_delta= argument of change_boxes / change_tracks: True (the
+    defaults of sigma_delta_mask) or (n_amp, v_min, v_max)."""
+    if sigma_delta is True:
+        return _sigma_delta_args(2, 2, _lib.SD_MAX_V)
+    if not isinstance(sigma_delta, (tuple, list)) or len(sigma_delta) != 3:
+        raise ValueError("sigma_delta must be True or (n_amp, v_min, v_max)")
+    return _sigma_delta_args(*sigma_delta)
+
+
+@dataclass
 class ChangeBoxes:
     """The connected components of a change mask (dips_mask_components):
     `counts` uint32 [n], the kept components per frame (not capped by K);
@@ -1063,6 +1111,84 @@ class DiffSeriesOperator:
                 ref.data_ptr() if ref is not None else None, _roi_arg(roi), k, flags, 1 if accumulate else 0,
                 background.data_ptr(), mask_out.data_ptr() if mask_out is not None and mask_out.numel() else None))
 
+    # -- the Sigma-Delta background (dips_diff_sigma_delta_mask) --------------
+    def sigma_delta_mask(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None, n_amp: int = 2,
+                         v_min: int = 2, v_max: int = 510,
+                         state: Optional[SigmaDelta] = None) -> Tuple[ChangeMask, SigmaDelta]:
+        """The change mask of every frame under a per-pixel adaptive
+        threshold: each pixel keeps a running median M of its integer
+        intensity J = max + min of R, G, B and an estimate V of its own
+        activity (both move by at most 1 per frame, V toward n_amp times the
+        deviation, inside [v_min, v_max]) and fires when |J - M| > V.  Returns
+        the mask and the state after the last frame.  The state starts at M =
+        J(ref) (None: frame 0), V = v_min, or continues `state`, the
+        SigmaDelta an earlier call over the same region returned -- a clip in
+        chunks.  The operator's mode and tau are not consulted."""
+        frames = _as_u8(frames)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        c = int(self.fmt)
+        n_amp, v_min, v_max = _sigma_delta_args(n_amp, v_min, v_max)
+        if state is not None:
+            if ref is not None:
+                raise ValueError("ref and state exclude each other")
+            if not isinstance(state, SigmaDelta):
+                raise ValueError("state must be a SigmaDelta")
+            sd = np.array(state.state, dtype=np.uint16, order="C")
+            if sd.shape != (_lib.SD_PLANES, rh, rw):
+                raise ValueError("state must hold the Sigma-Delta state of the same region")
+        else:
+            if ref is None and n == 0:
+                raise ValueError("the initial state needs ref or a frame")
+            sd = np.zeros((_lib.SD_PLANES, rh, rw), dtype=np.uint16)
+        out = np.zeros((n, rh, 4 * ((rw + 31) // 32)), dtype=np.uint8)
+        rp = None
+        if ref is not None:
+            ref = _as_u8(ref)
+            if ref.size != h * w * c:
+                raise ValueError("ref must have the shape of one frame")
+            rp = ref.ctypes.data
+        self._host.check(self._host._lib.dips_diff_sigma_delta_mask(
+            self._host.ptr, w, h, frames.ctypes.data if n else None, n, rp, _roi_arg(roi), n_amp, v_min, v_max,
+            1 if state is not None else 0, sd.ctypes.data, out.ctypes.data if out.size else None))
+        return ChangeMask(out, rw), SigmaDelta(sd)
+
+    def run_sigma_delta_mask_device(self, frames, state, mask_out=None, roi=None, ref=None, n_amp: int = 2,
+                                    v_min: int = 2, v_max: int = 510, accumulate: bool = False, stream=None) -> None:
+        """Asynchronous: frames / ref uint8 device tensors, state a 2-byte
+        device tensor of shape [2, h, w] of the region, overwritten or
+        (accumulate: ref must be None) continued; mask_out a uint8 device
+        tensor of shape [N, h, row_bytes] of the region (4-byte aligned),
+        every byte of which is written, or None for the state alone."""
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        c = int(self.fmt)
+        n_amp, v_min, v_max = _sigma_delta_args(n_amp, v_min, v_max)
+        if tuple(state.shape) != (_lib.SD_PLANES, rh, rw) or state.element_size() != 2:
+            raise ValueError("state must be a 2-byte tensor of shape [2, h, w] of the region")
+        if mask_out is not None and tuple(mask_out.shape) != (n, rh, 4 * ((rw + 31) // 32)):
+            raise ValueError("mask_out must be a uint8 tensor of shape [N, h, 4 * ceil(w / 32)] of the region")
+        for t in (frames, state, mask_out, ref):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        import torch
+        for t in (frames, mask_out, ref):
+            if t is not None and t.dtype != torch.uint8:
+                raise ValueError("frames, ref and mask_out must be uint8 tensors")
+        if ref is not None and ref.numel() != h * w * c:
+            raise ValueError("ref must have the size of one frame")
+        if accumulate and ref is not None:
+            raise ValueError("ref and accumulate exclude each other")
+        if not accumulate and ref is None and n == 0:
+            raise ValueError("the initial state needs ref or a frame")
+        lib = self._dev._lib
+        with _stream_of(self._dev, frames, stream):
+            self._dev.check(lib.dips_diff_sigma_delta_mask(
+                self._dev.ptr, w, h, frames.data_ptr() if n else None, n,
+                ref.data_ptr() if ref is not None else None, _roi_arg(roi), n_amp, v_min, v_max,
+                1 if accumulate else 0, state.data_ptr(),
+                mask_out.data_ptr() if mask_out is not None and mask_out.numel() else None))
+
     # -- the connected components of a change mask (dips_mask_components) ----
     def mask_components(self, mask: ChangeMask, connectivity: int = 8, min_area: int = 1, max_boxes: int = 64,
                         labels: bool = False, chunk_frames: int = 0) -> ChangeBoxes:
@@ -1260,11 +1386,14 @@ class DiffSeriesOperator:
                 self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, op, shape, rx, ry,
                 out.data_ptr() if n else None))
 
-    def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args):
+    def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args, sigma_delta=None):
         """(mask, region width, region height, n): the change mask of
         change_boxes / change_tracks as a device tensor, behind its morph
         steps; check_args(n) runs once the geometry is known."""
         import torch
+        if sigma_delta is not None and background is not None:
+            raise ValueError("sigma_delta and background exclude each other")
+        sd = _sigma_delta_option(sigma_delta) if sigma_delta is not None else None
         dev = torch.device("cuda", self._dev.device)
 
         def on_device(a):
@@ -1282,10 +1411,15 @@ class DiffSeriesOperator:
             _background_args(bg_k, bg_sel)
             if n == 0 and ref is None:
                 raise ValueError("the initial background needs ref or a frame")
+        if sd is not None and n == 0 and ref is None:
+            raise ValueError("the initial state needs ref or a frame")
         if ref is not None:
             ref = ref.reshape(-1)
         mask = torch.empty((n, rh, 4 * ((rw + 31) // 32)), dtype=torch.uint8, device=dev)
-        if background is None:
+        if sd is not None:
+            state = torch.empty((_lib.SD_PLANES, rh, rw), dtype=torch.int16, device=dev)
+            self.run_sigma_delta_mask_device(frames, state, mask, roi=roi, ref=ref, n_amp=sd[0], v_min=sd[1], v_max=sd[2])
+        elif background is None:
             self.run_change_mask_device(frames, mask, roi=roi, ref=ref)
         else:
             bg = torch.empty((int(self.fmt), rh, rw), dtype=torch.int16, device=dev)
@@ -1298,7 +1432,8 @@ class DiffSeriesOperator:
         return mask, rw, rh, n
 
     def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
-                     max_boxes: int = 64, labels: bool = False, morph=None, background=None) -> ChangeBoxes:
+                     max_boxes: int = 64, labels: bool = False, morph=None, background=None,
+                     sigma_delta=None) -> ChangeBoxes:
         """change_mask, then mask_components, with the mask kept on the
         device between the two: the moving objects of every frame.  frames /
         ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
@@ -1306,11 +1441,13 @@ class DiffSeriesOperator:
         to the mask before its components are taken (None: none).
         background: None, or rate_shift or (rate_shift, selective) to take
         the mask against the running-average background (background_mask)
-        instead of the operator's mode."""
+        instead of the operator's mode.  sigma_delta: None, or True or
+        (n_amp, v_min, v_max) to take the mask under the Sigma-Delta model's
+        per-pixel threshold (sigma_delta_mask); it excludes background."""
         import torch
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
-            lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_))
+            lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta)
         dev, k = mask.device, int(max_boxes)
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
@@ -1323,7 +1460,7 @@ class DiffSeriesOperator:
         return ChangeBoxes(to_u32(counts), to_u32(boxes), to_u32(lab) if lab is not None else None)
 
     def change_tracks(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
-                      max_boxes: int = 64, morph=None, background=None) -> ChangeTracks:
+                      max_boxes: int = 64, morph=None, background=None, sigma_delta=None) -> ChangeTracks:
         """change_mask, then mask_tracks, with the mask kept on the device
         between the two: the moving objects of every frame and their
         identity from frame to frame.  The arguments are change_boxes'; the
@@ -1331,7 +1468,7 @@ class DiffSeriesOperator:
         import torch
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
-            lambda n_: _tracks_args(connectivity, min_area, max_boxes, 0, n_))
+            lambda n_: _tracks_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta)
         dev, k = mask.device, int(max_boxes)
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
@@ -1551,7 +1688,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "ChangeTracks", "Background", "mask_row_bytes", "grid_cell",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "ChangeTracks", "Background", "SigmaDelta", "mask_row_bytes", "grid_cell",
     "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",

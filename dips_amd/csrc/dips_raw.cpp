@@ -64,6 +64,14 @@
 //            --background-out gets the final state, channel planes of roi_h x
 //            roi_w little-endian u16, and the stdout line ends with
 //            background=K[,selective]
+//            [--sigma-delta N[,VMIN[,VMAX]] [--sigma-delta-out FILE]] -> with
+//            --mask, --boxes or --tracks, and not with --background: the mask
+//            is taken under the Sigma-Delta model's per-pixel threshold with
+//            dips_diff_sigma_delta_mask (n_amp N in 1 .. 15, v_min 2 and v_max
+//            510 unless given, starting at frame 0); --sigma-delta-out gets
+//            the final state, the planes M and V of roi_h x roi_w
+//            little-endian u16, and the stdout line ends with
+//            sigma_delta=N,VMIN,VMAX
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -133,6 +141,7 @@ int usage() {
                  "                [--tracks FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
                  "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask, --boxes or --tracks)\n"
                  "                [--background K[,selective] [--background-out FILE]] (with --mask, --boxes or --tracks)\n"
+                 "                [--sigma-delta N[,VMIN[,VMAX]] [--sigma-delta-out FILE]] (likewise; not with --background)\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -207,10 +216,50 @@ bool parse_background(const std::string& s, BackgroundOpt* b) {
     return true;
 }
 
+// --sigma-delta: n_amp, v_min and v_max of dips_diff_sigma_delta_mask.
+struct SigmaDeltaOpt {
+    bool on = false;
+    uint32_t n_amp = 0, v_min = 2, v_max = DIPS_SD_MAX_V;
+    const char* out_path = nullptr;
+};
+
+// N[,VMIN[,VMAX]]
+bool parse_sigma_delta(const std::string& s, SigmaDeltaOpt* d) {
+    uint32_t* fields[3] = {&d->n_amp, &d->v_min, &d->v_max};
+    size_t pos = 0;
+    for (int k = 0; k < 3; ++k) {
+        const size_t comma = s.find(',', pos);
+        if (!parse_u32_or_zero(s.substr(pos, comma == std::string::npos ? comma : comma - pos).c_str(), fields[k])) return false;
+        if (comma == std::string::npos) {
+            pos = comma;
+            break;
+        }
+        pos = comma + 1;
+    }
+    if (pos != std::string::npos) return false;  // a fourth field
+    if (d->n_amp == 0 || d->n_amp > DIPS_SD_MAX_AMP || d->v_min > d->v_max || d->v_max > DIPS_SD_MAX_V) return false;
+    d->on = true;
+    return true;
+}
+
+// The u16 values of the state --background or --sigma-delta keeps for a
+// region of rw x rh pixels (1: neither is on, or the library will refuse).
+size_t state_values(bool sane, const BackgroundOpt& bg, const SigmaDeltaOpt& sd, uint32_t format, uint32_t rw, uint32_t rh) {
+    if (!sane || (!bg.on && !sd.on)) return 1u;
+    return (size_t)(sd.on ? DIPS_SD_PLANES : format) * rw * rh;
+}
+
 // The region's mask for --mask and --boxes: dips_diff_change_mask, or with
-// --background dips_diff_background_mask, whose final state goes to `state`.
+// --background dips_diff_background_mask, or with --sigma-delta
+// dips_diff_sigma_delta_mask, whose final state goes to `state`.
 int region_mask(dips_handle* hd, uint32_t w, uint32_t h, const uint8_t* frames, uint32_t n, const uint32_t* roi,
-                const BackgroundOpt& bg, std::vector<uint16_t>& state, uint8_t* mask, const char** what) {
+                const BackgroundOpt& bg, const SigmaDeltaOpt& sd, std::vector<uint16_t>& state, uint8_t* mask,
+                const char** what) {
+    if (sd.on) {
+        *what = "dips_diff_sigma_delta_mask";
+        return dips_diff_sigma_delta_mask(hd, w, h, frames, n, nullptr, roi, sd.n_amp, sd.v_min, sd.v_max, 0u, state.data(),
+                                          mask);
+    }
     if (!bg.on) {
         *what = "dips_diff_change_mask";
         return dips_diff_change_mask(hd, w, h, frames, n, nullptr, roi, mask);
@@ -219,19 +268,22 @@ int region_mask(dips_handle* hd, uint32_t w, uint32_t h, const uint8_t* frames, 
     return dips_diff_background_mask(hd, w, h, frames, n, nullptr, roi, bg.rate_shift, bg.flags, 0u, state.data(), mask);
 }
 
-// The final background state as raw u16 planes (0: written or not asked for).
-int write_background(const BackgroundOpt& bg, const std::vector<uint16_t>& state) {
-    if (!bg.out_path) return 0;
-    std::FILE* f = std::fopen(bg.out_path, "wb");
+// The final background or Sigma-Delta state as raw u16 planes (0: written or
+// not asked for).
+int write_background(const BackgroundOpt& bg, const SigmaDeltaOpt& sd, const std::vector<uint16_t>& state) {
+    const char* path = sd.on ? sd.out_path : bg.out_path;
+    if (!path) return 0;
+    std::FILE* f = std::fopen(path, "wb");
     if (!f || std::fwrite(state.data(), sizeof(uint16_t), state.size(), f) != state.size() || std::fclose(f) != 0) {
-        std::fprintf(stderr, "dips_raw: cannot write %s\n", bg.out_path);
+        std::fprintf(stderr, "dips_raw: cannot write %s\n", path);
         return 1;
     }
     return 0;
 }
 
-void print_background(const BackgroundOpt& bg) {
+void print_background(const BackgroundOpt& bg, const SigmaDeltaOpt& sd) {
     if (bg.on) std::printf(" background=%u%s", bg.rate_shift, bg.flags ? ",selective" : "");
+    if (sd.on) std::printf(" sigma_delta=%u,%u,%u", sd.n_amp, sd.v_min, sd.v_max);
 }
 
 // The steps in order on the host mask of n frames of rw x rh pixels; the
@@ -525,6 +577,7 @@ int run_series(int argc, char** argv) {
     bool has_box_opt = false;
     std::vector<MorphStep> morph;
     BackgroundOpt bg;
+    SigmaDeltaOpt sd;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -566,6 +619,10 @@ int run_series(int argc, char** argv) {
             if (!parse_background(argv[++i], &bg)) return usage();
         } else if (a == "--background-out" && has) {
             bg.out_path = argv[++i];
+        } else if (a == "--sigma-delta" && has) {
+            if (!parse_sigma_delta(argv[++i], &sd)) return usage();
+        } else if (a == "--sigma-delta-out" && has) {
+            sd.out_path = argv[++i];
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -577,6 +634,8 @@ int run_series(int argc, char** argv) {
     if (!morph.empty() && !mask_path && !boxes_path && !tracks_path) return usage();
     // --background belongs to --mask, --boxes or --tracks, --background-out to --background
     if ((bg.on && !mask_path && !boxes_path && !tracks_path) || (bg.out_path && !bg.on)) return usage();
+    // so does --sigma-delta, --sigma-delta-out to --sigma-delta; the two models exclude each other
+    if ((sd.on && !mask_path && !boxes_path && !tracks_path) || (sd.out_path && !sd.on) || (sd.on && bg.on)) return usage();
     // --roi belongs to --grid, --pixel-sums, --mask, --pixel-times, --boxes or --tracks
     if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path && !boxes_path && !tracks_path) return usage();
     if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) +
@@ -656,9 +715,9 @@ int run_series(int argc, char** argv) {
                           (uint64_t)rw * rh < (1ull << 30);
         const uint32_t row_bytes = dips_mask_row_bytes(rw);
         std::vector<uint8_t> mask(sane ? (size_t)n * rh * row_bytes : 1u);
-        std::vector<uint16_t> state(sane && bg.on ? (size_t)p.format * rw * rh : 1u);
+        std::vector<uint16_t> state(state_values(sane, bg, sd, p.format, rw, rh));
         const char* what = nullptr;
-        st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, state, mask.data(), &what);
+        st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, sd, state, mask.data(), &what);
         if (st == DIPS_OK && !morph.empty()) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
@@ -670,7 +729,7 @@ int run_series(int argc, char** argv) {
         }
         dips_destroy(hd);
         if (n == 0) mask.clear();
-        if (write_background(bg, state) != 0) return 1;
+        if (write_background(bg, sd, state) != 0) return 1;
         // frames x roi_h x row_bytes, bit i of a row = bit (i & 7) of byte (i >> 3)
         std::FILE* f = std::fopen(mask_path, "wb");
         if (!f || std::fwrite(mask.data(), 1, mask.size(), f) != mask.size() || std::fclose(f) != 0) {
@@ -682,7 +741,7 @@ int run_series(int argc, char** argv) {
         std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu", has_roi ? roi[0] : 0u,
                     has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
-        print_background(bg);
+        print_background(bg, sd);
         std::printf("\n");
         return 0;
     }
@@ -701,9 +760,9 @@ int run_series(int argc, char** argv) {
         std::vector<uint32_t> counts(sane ? (size_t)n : 1u), recs(sane ? (size_t)n * max_boxes * DIPS_BOX_WORDS : 1u);
         std::vector<uint32_t> links(sane && tracks ? (size_t)n * max_boxes * DIPS_LINK_WORDS : 1u);
         std::vector<uint32_t> ids(sane && tracks ? 1u + 2u * (size_t)max_boxes : 1u);  // the state: [0] counts the tracks
-        std::vector<uint16_t> state(sane && bg.on ? (size_t)p.format * rw * rh : 1u);
+        std::vector<uint16_t> state(state_values(sane, bg, sd, p.format, rw, rh));
         const char* what = nullptr;
-        st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, state, mask.data(), &what);
+        st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, sd, state, mask.data(), &what);
         if (st == DIPS_OK && !morph.empty()) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
@@ -723,7 +782,7 @@ int run_series(int argc, char** argv) {
             return rc;
         }
         dips_destroy(hd);
-        if (write_background(bg, state) != 0) return 1;
+        if (write_background(bg, sd, state) != 0) return 1;
         std::FILE* f = std::fopen(out_path, "w");
         if (!f) {
             std::fprintf(stderr, "dips_raw: cannot write %s\n", out_path);
@@ -755,7 +814,7 @@ int run_series(int argc, char** argv) {
                     min_area, max_boxes, total, stored);
         if (tracks) std::printf(" tracks=%u", ids[0]);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
-        print_background(bg);
+        print_background(bg, sd);
         std::printf("\n");
         return 0;
     }

@@ -13,6 +13,7 @@
 
 #include "dips_handle.h"
 #include "dips_kernels.h"
+#include "series_sigma_delta.h"
 
 using dips_abi::guard;
 using namespace dips_internal;
@@ -860,22 +861,26 @@ struct BgGeom {
 // slower at 4K than this rule, DESIGN.md.)  Refused (the
 // generic kernel runs): frames of 2^31 bytes or more, 2^28 frames, regions
 // whose padded rows hold 2^31 vecs or more.
+// `kernel_ptr` / `unroll`: the kernel family and its vecs per lane (the
+// Sigma-Delta model shares the schedule, sigma_delta_geometry).
 BgGeom background_geometry(dips_handle* h, uint32_t width, uint32_t height, uint32_t n_frames, int C,
-                           const dips::GridSpec& g) {
+                           const dips::GridSpec& g,
+                           const void* (*kernel_ptr)(int, int, bool) = dips::series_background_kernel_ptr,
+                           int unroll = dips::kUnrollBackground) {
     BgGeom q;
     const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
     if (fb >= (1ull << 31) || n_frames == 0 || n_frames >= (1u << 28)) return q;
     const uint64_t nvec8 = 8u * mask_words_per_row(g.w) * g.h;
     if (nvec8 == 0 || nvec8 >= (1ull << 31)) return q;
     auto resident_of = [&](bool small_tile) -> uint64_t {
-        const void* k = dips::series_background_kernel_ptr(C, (int)h->p.chroma_filter, small_tile);
+        const void* k = kernel_ptr(C, (int)h->p.chroma_filter, small_tile);
         if (!k) return 0;
         return waves_per_simd((uint64_t)occupancy_blocks(h, k), true) * (uint64_t)h->cu_count * 4u;
     };
-    uint64_t vpt = 64u * (uint64_t)dips::kUnrollBackground;  // vecs per tile
+    uint64_t vpt = 64u * (uint64_t)unroll;  // vecs per tile
     uint64_t resident = resident_of(false);
     if (resident == 0) return q;
-    if (dips::kUnrollBackground > 1 && 2u * ((nvec8 + vpt - 1) / vpt) < resident) {
+    if (unroll > 1 && 2u * ((nvec8 + vpt - 1) / vpt) < resident) {
         q.small_tile = true;
         vpt = 64u;
         resident = resident_of(true);
@@ -976,6 +981,110 @@ dips_status run_background_device(dips_handle* h, uint32_t width, uint32_t heigh
     } else {
         if ((uint64_t)g.h * wpr >= (1ull << 31))
             return fail(h, DIPS_ERR_INVALID, "diff_background_mask: region too large for the generic kernel");
+        dips_status st = launch_generic(0u, g.h, 0u, (uint32_t)wpr, 0u);
+        if (st != DIPS_OK) return st;
+    }
+    if (timing) {
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+    }
+    return DIPS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The Sigma-Delta background and its per-pixel adaptive threshold mask
+// (dips_diff_sigma_delta_mask; kernels in series_sigma_delta.hip)
+// ---------------------------------------------------------------------------
+
+// Run the Sigma-Delta model on device pointers, asynchronously on `s`: the
+// schedule of run_background_device (background_geometry with this kernel
+// family and its vecs per lane; the generic kernel first for the words whose
+// vecs the fast kernel leaves out).  ref0: the frame the initial M is taken
+// from (accumulate false), else unused.  n_frames may be 0 (accumulate false:
+// the initial state is written).
+dips_status run_sigma_delta_device(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames,
+                                   uint32_t n_frames, const uint8_t* ref0, const dips::GridSpec& g, uint32_t n_amp,
+                                   uint32_t v_min, uint32_t v_max, bool accumulate, uint16_t* state, uint8_t* mask,
+                                   hipStream_t s) {
+    const int C = (int)h->p.format;
+    const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+    const uint64_t wpr = mask_words_per_row(g.w);
+    const uint64_t mfb = wpr * g.h * 4u;
+    BgGeom q;
+    // GRAY8 has no fast form; DIPS_FLAG_CROSSCHECK asks for the plain kernel
+    if (C != 1 && !(h->p.flags & DIPS_FLAG_FORCE_GENERIC) && !h->crosscheck())
+        q = background_geometry(h, width, height, n_frames, C, g, dips::series_sigma_delta_kernel_ptr,
+                                dips::kUnrollSigmaDelta);
+    auto launch_generic = [&](uint32_t row0, uint32_t n_rows, uint32_t word0, uint32_t n_words,
+                              uint32_t state_x0) -> dips_status {
+        dips::SdGenericArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.state = state;
+        a.mask = mask;
+        a.frame_bytes = fb;
+        a.mask_frame_bytes = mfb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.chroma = C == 1 ? 0u : h->p.chroma_filter;
+        a.n_amp = n_amp;
+        a.v_min = v_min;
+        a.v_max = v_max;
+        a.accumulate = accumulate ? 1u : 0u;
+        a.row0 = row0;
+        a.n_rows = n_rows;
+        a.word0 = word0;
+        a.n_words = n_words;
+        a.state_x0 = state_x0;
+        a.roi = dips::GridRect{g.x, g.y, g.w, g.h};
+        DIPS_HIP(h, dips::launch_sigma_delta_generic(a, C, s));
+        return DIPS_OK;
+    };
+
+    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventReturn ev_return{h, &e0, &e1};
+    if (timing) {
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        DIPS_HIP(h, hipEventRecord(e0, s));
+    }
+    if (q.ok) {
+        // the partial last vec of the region's last rows that would read past
+        // the frame's end: its whole mask word and its pixels' state come
+        // from the generic kernel, launched BEFORE the fast kernel overwrites
+        // the state an accumulating call continues (run_background_device)
+        if (g.w % 4u != 0u) {
+            const uint32_t i0 = (g.w - 1u) & ~3u;  // the last vec of a region row
+            const uint64_t npx = (uint64_t)width * height;
+            for (uint32_t r = g.h; r-- > 0 && g.h - r <= 4u;) {
+                if ((uint64_t)(g.y + r) * width + g.x + i0 + 4u <= npx) break;  // it and every earlier row fit
+                dips_status st = launch_generic(r, 1u, (g.w - 1u) >> 5, 1u, i0);
+                if (st != DIPS_OK) return st;
+            }
+        }
+        dips::SdArgs a{};
+        a.frames = frames;
+        a.ref0 = ref0;
+        a.state = state;
+        a.mask = mask;
+        a.frame_bytes = (uint32_t)fb;
+        a.mask_frame_bytes = (uint32_t)mfb;
+        a.width = width;
+        a.n_frames = n_frames;
+        a.n_tiles = (uint32_t)q.n_tiles;
+        a.n_waves = (uint32_t)q.n_waves;
+        a.n_amp = n_amp;
+        a.v_min = v_min;
+        a.v_max = v_max;
+        a.accumulate = accumulate ? 1u : 0u;
+        a.roi = dips::GridRect{g.x, g.y, g.w, g.h};
+        DIPS_HIP(h, dips::launch_series_sigma_delta(a, C, (int)h->p.chroma_filter, q.small_tile, (uint32_t)q.blocks, s));
+    } else {
+        if ((uint64_t)g.h * wpr >= (1ull << 31))
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: region too large for the generic kernel");
         dips_status st = launch_generic(0u, g.h, 0u, (uint32_t)wpr, 0u);
         if (st != DIPS_OK) return st;
     }
@@ -1754,6 +1863,67 @@ dips_status dips_diff_background_mask(dips_handle* h, uint32_t width, uint32_t h
                                    mask_bytes ? h->stage_map.as<uint8_t>() : nullptr, h->stream);
         if (st != DIPS_OK) return st;
         DIPS_HIP(h, hipMemcpyAsync(background, h->stage_series.p, state_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (mask_bytes) DIPS_HIP(h, hipMemcpyAsync(mask, h->stage_map.p, mask_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_diff_sigma_delta_mask(dips_handle* h, uint32_t width, uint32_t height, const uint8_t* frames,
+                                       uint32_t n_frames, const uint8_t* ref, const uint32_t* roi, uint32_t n_amp,
+                                       uint32_t v_min, uint32_t v_max, uint32_t accumulate, uint16_t* state,
+                                       uint8_t* mask) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_amp == 0u || n_amp > DIPS_SD_MAX_AMP)
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: n_amp must be 1 .. 15");
+        if (v_min > v_max || v_max > DIPS_SD_MAX_V)
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: 0 <= v_min <= v_max <= 510 is required");
+        if (!state || (!frames && n_frames > 0))
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: null argument");
+        const bool acc = accumulate != 0u;
+        if (acc && ref)
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: ref must be NULL when accumulating");
+        if (!acc && !ref && n_frames == 0)
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: the initial state needs ref or a frame");
+        dips::GridSpec g{};
+        if (const char* why = grid_spec(width, height, roi, 1u, 1u, &g))
+            return fail(h, DIPS_ERR_INVALID, std::string("diff_sigma_delta_mask: ") + why);
+        const uint64_t n_px = (uint64_t)g.w * g.h;
+        if (n_px >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: the region must stay below 2^30 pixels");
+        const bool dev = (h->p.flags & DIPS_FLAG_DEVICE_PTRS) != 0;
+        if (dev && ((uintptr_t)state & 1u) != 0)
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: the device state must be 2-byte aligned");
+        if (dev && ((uintptr_t)mask & 3u) != 0)
+            return fail(h, DIPS_ERR_INVALID, "diff_sigma_delta_mask: the device mask must be 4-byte aligned");
+        if (n_frames == 0 && acc) return DIPS_OK;  // nothing to fold
+        const int C = (int)h->p.format;
+        const uint64_t fb = (uint64_t)width * height * (uint64_t)C;
+        if (dev)
+            return run_sigma_delta_device(h, width, height, frames, n_frames, acc ? nullptr : (ref ? ref : frames), g,
+                                          n_amp, v_min, v_max, acc, state, mask, h->stream);
+        // host pointers: stage through HBM (synchronous call)
+        const size_t total = (size_t)fb * n_frames;
+        const size_t state_bytes = sizeof(uint16_t) * (size_t)DIPS_SD_PLANES * (size_t)n_px;
+        const size_t mask_bytes = mask ? (size_t)(4u * mask_words_per_row(g.w) * g.h) * n_frames : 0u;
+        if (total) DIPS_HIP(h, h->stage_frames.ensure(total));
+        DIPS_HIP(h, h->stage_series.ensure(state_bytes));
+        if (mask_bytes) DIPS_HIP(h, h->stage_map.ensure(mask_bytes));
+        if (total) DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, frames, total, hipMemcpyHostToDevice, h->stream));
+        if (acc) DIPS_HIP(h, hipMemcpyAsync(h->stage_series.p, state, state_bytes, hipMemcpyHostToDevice, h->stream));
+        const uint8_t* ref_dev = acc ? nullptr : h->stage_frames.as<uint8_t>();
+        if (ref) {
+            DIPS_HIP(h, h->stage_ref.ensure(fb));
+            DIPS_HIP(h, hipMemcpyAsync(h->stage_ref.p, ref, fb, hipMemcpyHostToDevice, h->stream));
+            ref_dev = h->stage_ref.as<uint8_t>();
+        }
+        st = run_sigma_delta_device(h, width, height, total ? h->stage_frames.as<uint8_t>() : nullptr, n_frames, ref_dev,
+                                    g, n_amp, v_min, v_max, acc, h->stage_series.as<uint16_t>(),
+                                    mask_bytes ? h->stage_map.as<uint8_t>() : nullptr, h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(state, h->stage_series.p, state_bytes, hipMemcpyDeviceToHost, h->stream));
         if (mask_bytes) DIPS_HIP(h, hipMemcpyAsync(mask, h->stage_map.p, mask_bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;

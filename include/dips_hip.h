@@ -434,6 +434,51 @@ dips_status dips_diff_background_mask(dips_handle *h, uint32_t width, uint32_t h
                                       const uint32_t *roi, uint32_t rate_shift, uint32_t bg_flags,
                                       uint32_t accumulate, uint16_t *background, uint8_t *mask);
 
+/* The Sigma-Delta background model of a region of interest and its change
+ * mask: a threshold that adapts per pixel, where every other mask compares
+ * with one global tau (Manzanera & Richefeu, 2007).  The reference has no
+ * counterpart.  Exact and integer: no f32, no rate multiply, no tau.
+ * It works in the integer intensity J of a pixel, 0 <= J <= 510: max + min of
+ * the R, G, B bytes with no chroma filter, 2 * channel with
+ * DIPS_CHROMA_R / G / B, 2 * g for GRAY8; RGBA8's alpha never enters.
+ * State: per region pixel two u16, a running median M of J (0 <= M <= 510)
+ * and a running estimate V of the pixel's own temporal activity (v_min <= V
+ * <= v_max).  Parameters: n_amp N in 1 .. 15, 0 <= v_min <= v_max <= 510.
+ * For frame t, in order, per pixel (update, then decide):
+ *   M' = M + sgn(J_t - M)
+ *   D  = |J_t - M'|
+ *   V' = clamp(V + sgn(N * D - V), v_min, v_max)   if D != 0, else V' = V
+ *   bit(t, j, i) = D > V'                          strict, like every mask
+ * M cannot leave [0, 510], since it moves toward a J inside it; N * D <= 7650
+ * and every difference above fits a signed 16-bit lane (the kernels rely on
+ * it).  params.tau and params.mode are not consulted; chroma_filter is.
+ * accumulate == 0: the initial state is M = J(ref) (ref == NULL: J(frames[0]),
+ * so frame 0 is all zero) and V = v_min; with n_frames == 0 the call writes
+ * that initial state (ref is then required).  accumulate != 0: the state the
+ * buffer holds is continued and ref must be NULL; nothing is written when
+ * n_frames == 0; the caller promises that the held V lies in [v_min, v_max]
+ * and M in [0, 510].  A clip of any length goes chunk by chunk, bit for bit.
+ * Layout of state: DIPS_SD_PLANES planes of w * h u16, state[p*w*h + j*w + i]
+ * with plane 0 = M and plane 1 = V, each plane an image; required, 2-byte
+ * aligned, written in full.  mask: exactly dips_diff_change_mask's layout
+ * (pad bits 0, every byte written), or NULL for the state alone.
+ * roi, format, DIPS_FLAG_DEVICE_PTRS (asynchronous on the handle's stream;
+ * mask 4-byte aligned) and host pointers (staged through HBM, synchronous,
+ * the state uploaded first when accumulating) as in
+ * dips_diff_background_mask.  DIPS_ERR_INVALID, the outputs untouched, for
+ * n_amp of 0 or > 15, v_min > v_max, v_max > 510, null frames with n_frames
+ * > 0, null state, ref given with accumulate, no ref and no frames without
+ * accumulate, a misaligned device state or mask, the roi errors of
+ * dips_grid_cell (at rows = cols = 1) and a region of 2^30 pixels or more. */
+#define DIPS_SD_MAX_AMP 15u
+#define DIPS_SD_MAX_V 510u
+#define DIPS_SD_PLANES 2u
+dips_status dips_diff_sigma_delta_mask(dips_handle *h, uint32_t width, uint32_t height,
+                                       const uint8_t *frames, uint32_t n_frames, const uint8_t *ref,
+                                       const uint32_t *roi, uint32_t n_amp, uint32_t v_min,
+                                       uint32_t v_max, uint32_t accumulate, uint16_t *state,
+                                       uint8_t *mask);
+
 /* The connected components of a change mask, frame by frame: the blobs and
  * bounding boxes the README promises the mask "feeds" (difference ->
  * threshold -> components -> boxes).  The reference has no counterpart.  A

@@ -56,6 +56,9 @@ pub const DIPS_MORPH_DIAMOND: u32 = 1;
 pub const DIPS_MORPH_MAX_RADIUS: u32 = 15;
 pub const DIPS_BG_SELECTIVE: u32 = 1;
 pub const DIPS_BG_MAX_RATE_SHIFT: u32 = 8;
+pub const DIPS_SD_MAX_AMP: u32 = 15;
+pub const DIPS_SD_MAX_V: u32 = 510;
+pub const DIPS_SD_PLANES: u32 = 2;
 
 /// `dips_params`: ComputeState::new's arguments (dips/src/gpu/mod.rs:59-65,
 /// DiPsProperties dips/src/lib.rs:63-86) + the batch series configuration.
@@ -200,6 +203,9 @@ extern "C" {
     pub fn dips_diff_background_mask(h: *mut DipsHandle, width: u32, height: u32, frames: *const u8, n_frames: u32,
                                      reference: *const u8, roi: *const u32, rate_shift: u32, bg_flags: u32,
                                      accumulate: u32, background: *mut u16, mask: *mut u8) -> DipsStatus;
+    pub fn dips_diff_sigma_delta_mask(h: *mut DipsHandle, width: u32, height: u32, frames: *const u8, n_frames: u32,
+                                      reference: *const u8, roi: *const u32, n_amp: u32, v_min: u32, v_max: u32,
+                                      accumulate: u32, state: *mut u16, mask: *mut u8) -> DipsStatus;
     pub fn dips_mask_components(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32,
                                 connectivity: u32, min_area: u32, max_boxes: u32, chunk_frames: u32,
                                 counts: *mut u32, boxes: *mut u32, labels: *mut u32) -> DipsStatus;
