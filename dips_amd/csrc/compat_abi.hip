@@ -388,14 +388,8 @@ dips_status batch_steady(dips_handle* h, const uint8_t* bf, uint8_t* bo, uint32_
         }
         a.lut = h->cb_lut.as<uint16_t>();
     }
-    const bool timing = (h->p.flags & DIPS_FLAG_TIME_KERNEL) != 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) {
-        e0 = take_event(h);
-        e1 = take_event(h);
-        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
-        DIPS_HIP(h, hipEventRecord(e0, h->stream));
-    }
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(h->stream));
     if (filter_src)
         DIPS_HIP(h, dips::launch_compat_filter_frames(filter_src, const_cast<uint8_t*>(bf), width, height, m,
                                                       h->p.spatial_window_size, h->p.chroma_filter, h->stream));
@@ -406,10 +400,7 @@ dips_status batch_steady(dips_handle* h, const uint8_t* bf, uint8_t* bo, uint32_
     else
         DIPS_HIP(h, dips::launch_compat_batch(a, (int)h->p.chroma_filter, (int)h->p.filter_type, h->p.colorize != 0,
                                               fast, (uint32_t)((n_tiles * n_chunks + 3u) / 4u), h->stream));
-    if (timing) {
-        DIPS_HIP(h, hipEventRecord(e1, h->stream));
-        h->ev_pending.emplace_back(e0, e1);
-    }
+    DIPS_TRY(span.end(h->stream));
     if (swap) {
         // m >= 16: all four slots were rewritten
         for (int j = 0; j < 4; ++j) std::swap(h->slots[j], h->slots_alt[j]);

@@ -1,8 +1,9 @@
 // dips_abi.hip -- host side of include/dips_hip.h, part 1: the handle's
 // lifecycle (ComputeState::new / Drop, dips/src/gpu/mod.rs:59-165), its
 // stream, its errors and the kernel timing.  The dips-compat operator is in
-// compat_abi.hip, the difference series in series_abi.hip; the handle and
-// the shared helpers in dips_handle.h.  Every extern "C" body runs inside
+// compat_abi.hip, the difference series in series_abi.hip, its regional
+// products in region_abi.hip, the mask products in mask_abi.hip; the handle
+// and the shared helpers in dips_handle.h.  Every extern "C" body runs inside
 // dips_abi::guard (abi_guard.h): no C++ exception leaves the library.
 #include <hip/hip_runtime.h>
 

@@ -1,10 +1,16 @@
 // dips_handle.h -- the handle behind include/dips_hip.h's dips_* entry
-// points and the helpers its three translation units share (internal to
+// points and the helpers its translation units share (internal to
 // libdips_hip.so):
 //   dips_abi.hip    lifecycle, streams, errors, kernel timing
 //   compat_abi.hip  the dips-compat ComputeState (add_texture / dispatch /
 //                   frame_callback and the batch form)
 //   series_abi.hip  the north-star difference series and its measurement legs
+//   region_abi.hip  the regional products: grid, pixel sums, change mask,
+//                   pixel times, background and Sigma-Delta models
+//   mask_abi.hip    the mask products: components, tracks, morphology
+//   shard_abi.hip   the frame-range sharding of the series
+// (series_host.h: what the series, region and mask units share; series_sched.h:
+// their schedules as functions of plain numbers.)
 //
 // The handle plays the role of the reference's ComputeState
 // (dips/src/gpu/mod.rs:39-56): it owns the HIP device binding, the stream,
@@ -153,4 +159,57 @@ uint64_t series_waves(dips_handle* h, uint32_t width, uint32_t height, uint32_t 
     do {                                                                      \
         hipError_t e_ = (call);                                               \
         if (e_ != hipSuccess) return dips_internal::hip_fail((h), e_, #call); \
+    } while (0)
+
+namespace dips_internal {
+
+// The timed span of a launch function (DIPS_FLAG_TIME_KERNEL; does nothing
+// without the flag): begin(s) takes two events and records the first, end(s)
+// records the second and queues the pair in ev_pending -- one pair per call,
+// and only once both are recorded.  Events not queued go back to the
+// handle's free list when the launch function returns, however it returns.
+// take() alone, for what must be launched between taking the events and the
+// span's start.
+struct KernelSpan {
+    dips_handle* h;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit KernelSpan(dips_handle* handle) : h(handle) {}
+    KernelSpan(const KernelSpan&) = delete;
+    KernelSpan& operator=(const KernelSpan&) = delete;
+    ~KernelSpan() {
+        try {
+            if (e0) h->ev_free.push_back(e0);
+            if (e1) h->ev_free.push_back(e1);
+        } catch (...) {
+        }
+    }
+    dips_status take() {
+        if (!(h->p.flags & DIPS_FLAG_TIME_KERNEL) || e0) return DIPS_OK;
+        e0 = take_event(h);
+        e1 = take_event(h);
+        if (!e0 || !e1) return fail(h, DIPS_ERR_HIP, "hipEventCreate failed");
+        return DIPS_OK;
+    }
+    dips_status begin(hipStream_t s) {
+        const dips_status st = take();
+        if (st != DIPS_OK || !e0) return st;
+        DIPS_HIP(h, hipEventRecord(e0, s));
+        return DIPS_OK;
+    }
+    dips_status end(hipStream_t s) {
+        if (!e0) return DIPS_OK;
+        DIPS_HIP(h, hipEventRecord(e1, s));
+        h->ev_pending.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+        return DIPS_OK;
+    }
+};
+
+}  // namespace dips_internal
+
+// a dips_status expression's failure returned from the calling function
+#define DIPS_TRY(expr)                      \
+    do {                                    \
+        const dips_status st_ = (expr);     \
+        if (st_ != DIPS_OK) return st_;     \
     } while (0)

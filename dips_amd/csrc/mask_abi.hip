@@ -1,0 +1,389 @@
+// mask_abi.hip -- host side of include/dips_hip.h, part 5: the products of a
+// packed change mask -- its connected components, the components linked
+// across frames (tracks) and the binary morphology.  What they share with
+// the series and the regional products is in series_host.h.  Every
+// extern "C" body runs inside dips_abi::guard (abi_guard.h).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <string>
+
+#include "series_host.h"
+
+using dips_abi::guard;
+using namespace dips_internal;
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// The connected components of a mask (dips_mask_components; kernels in
+// mask_components.hip)
+// ---------------------------------------------------------------------------
+
+constexpr size_t kComponentsScratchBytes = (size_t)1 << 30;  // chunk_frames = 0 stays within this
+
+// The labelling's view of a w x hgt mask (components and tracks)
+dips::ComponentsArgs components_args(uint32_t w, uint32_t hgt, uint32_t connectivity, uint32_t min_area) {
+    dips::ComponentsArgs a{};
+    a.w = w;
+    a.h = hgt;
+    a.npx = w * hgt;
+    a.wpr = (uint32_t)mask_words_per_row(w);
+    a.hw = (w + 1u) / 2u;
+    a.nslots = a.hw * hgt;
+    a.wpf = a.wpr * hgt;
+    a.bpf = (a.wpf + 255u) / 256u;
+    a.connectivity = connectivity;
+    a.min_area = min_area;
+    return a;
+}
+
+// What dips_mask_components and dips_mask_tracks check of the region and the
+// box count alike, under the exported function's `name`
+dips_status check_labelling(dips_handle* h, const char* name, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                            uint32_t connectivity, uint32_t max_boxes) {
+    const std::string pre = std::string(name) + ": ";
+    if (connectivity != 4u && connectivity != 8u) return fail(h, DIPS_ERR_INVALID, pre + "connectivity must be 4 or 8");
+    if (roi_w == 0 || roi_h == 0 || roi_w >= (1u << 24) || roi_h >= (1u << 24))
+        return fail(h, DIPS_ERR_INVALID, pre + "roi_w and roi_h must be 1 .. 2^24 - 1");
+    if ((uint64_t)roi_w * roi_h >= (1ull << 30))
+        return fail(h, DIPS_ERR_INVALID, pre + "the region must stay below 2^30 pixels");
+    if ((uint64_t)n_frames * max_boxes * DIPS_BOX_WORDS >= (1ull << 32))
+        return fail(h, DIPS_ERR_INVALID, pre + "n_frames * max_boxes * 8 must stay below 2^32");
+    return DIPS_OK;
+}
+
+// the device pointers of a call, all 4-byte aligned
+dips_status check_aligned4(dips_handle* h, const char* name, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    if ((bits & 3u) != 0)
+        return fail(h, DIPS_ERR_INVALID, std::string(name) + ": the device pointers must be 4-byte aligned");
+    return DIPS_OK;
+}
+
+// Label the frames of a device mask, asynchronously on `s`, `chunk` frames
+// per round (0: automatic) in the handle's scratch.
+dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                                  uint32_t connectivity, uint32_t min_area, uint32_t max_boxes, uint32_t chunk,
+                                  uint32_t* counts, uint32_t* boxes, uint32_t* labels, hipStream_t s) {
+    dips::ComponentsArgs a = components_args(w, hgt, connectivity, min_area);
+    a.max_boxes = max_boxes;
+    // per frame: parent, six statistics (two of 8 bytes) per slot, the block sums
+    const size_t per_frame = 4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf;
+    uint64_t frames = chunk ? chunk : std::max<uint64_t>(1u, kComponentsScratchBytes / per_frame);
+    frames = std::min<uint64_t>(frames, n_frames);
+    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
+    const uint32_t F = (uint32_t)frames;
+    // the scratch before the timed span (growing it synchronises)
+    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F));
+    uint8_t* base = h->cc_scratch.as<uint8_t>();
+    a.sum_i = reinterpret_cast<uint64_t*>(base);
+    a.sum_j = a.sum_i + (size_t)F * a.nslots;
+    a.area = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);
+    a.min_x = a.area + (size_t)F * a.nslots;
+    a.max_x = a.min_x + (size_t)F * a.nslots;
+    a.max_y = a.max_x + (size_t)F * a.nslots;
+    a.parent = a.max_y + (size_t)F * a.nslots;
+    a.block_count = a.parent + (size_t)F * a.npx;
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    // the records no component fills are zeros
+    if (max_boxes != 0u)
+        DIPS_HIP(h, hipMemsetAsync(boxes, 0, sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes, s));
+    const size_t frame_words = (size_t)a.wpf;
+    for (uint32_t t = 0; t < n_frames; t += F) {
+        a.n_frames = std::min(F, n_frames - t);
+        a.mask = reinterpret_cast<const uint32_t*>(mask) + (size_t)t * frame_words;
+        a.counts = counts + t;
+        a.boxes = max_boxes != 0u ? boxes + (size_t)t * max_boxes * DIPS_BOX_WORDS : nullptr;
+        a.labels = labels ? labels + (size_t)t * a.npx : nullptr;
+        DIPS_HIP(h, dips::launch_mask_components(a, s));
+    }
+    return span.end(s);
+}
+
+// ---------------------------------------------------------------------------
+// The components of a mask linked across frames (dips_mask_tracks; kernels in
+// mask_components.hip and mask_tracks.hip)
+// ---------------------------------------------------------------------------
+
+// tr_ids_kernel walks a chain back to the chunk's first frame at most: the
+// cap keeps that walk, one dependent load per frame, short whatever the clip
+constexpr uint32_t kTracksChunkFrames = 256;
+
+// Label and link the frames of a device mask, asynchronously on `s`, `chunk`
+// frames per round (0: automatic) in the handle's scratch.  The parent and
+// label planes have one more frame in front, the predecessor of the chunk's
+// first frame: prev_mask is labelled into it, and what the runs of a chunk's
+// last frame own is copied there for the next chunk.  The next id and the last frame's tracks
+// and ages stay in the scratch from chunk to chunk (two buffers, swapped) and
+// move from and to `state` by copies in the stream.
+dips_status run_tracks_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                              uint32_t connectivity, uint32_t min_area, uint32_t K, uint32_t chunk,
+                              const uint8_t* prev_mask, uint32_t* state, uint32_t* counts, uint32_t* boxes,
+                              uint32_t* links, hipStream_t s) {
+    dips::ComponentsArgs a = components_args(w, hgt, connectivity, min_area);
+    // per frame: the labelling's share, the overlap table, cprev and hrank, heads and base;
+    // once: the plane in front of parent and of the labels, next id, a count, two carries
+    const size_t per_frame =
+        4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf + 4u * (size_t)K * K + 8u * (size_t)K + 8u;
+    const size_t fixed = 4u * (size_t)a.npx + 4u * (size_t)a.nslots + 16u * (size_t)K + 8u;
+    uint64_t frames =
+        chunk ? chunk
+              : std::max<uint64_t>(1u, (kComponentsScratchBytes - std::min(fixed, kComponentsScratchBytes)) / per_frame);
+    frames = std::min<uint64_t>(frames, n_frames);
+    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
+    frames = std::min<uint64_t>(frames, kTracksChunkFrames);
+    const uint32_t F = (uint32_t)frames;
+    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F + fixed));
+    uint8_t* base = h->cc_scratch.as<uint8_t>();
+    a.sum_i = reinterpret_cast<uint64_t*>(base);
+    a.sum_j = a.sum_i + (size_t)F * a.nslots;
+    uint32_t* label0 = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);  // F + 1 planes
+    a.area = label0 + a.nslots;
+    a.min_x = a.area + (size_t)F * a.nslots;
+    a.max_x = a.min_x + (size_t)F * a.nslots;
+    a.max_y = a.max_x + (size_t)F * a.nslots;
+    uint32_t* parent0 = a.max_y + (size_t)F * a.nslots;  // F + 1 planes
+    a.parent = parent0 + a.npx;
+    a.block_count = a.parent + (size_t)F * a.npx;
+
+    dips::TracksArgs tr{};
+    tr.parent = parent0;
+    tr.label = label0;
+    tr.ov = a.block_count + (size_t)F * a.bpf;
+    tr.cprev = tr.ov + (size_t)F * K * K;
+    tr.hrank = tr.cprev + (size_t)F * K;
+    tr.heads = tr.hrank + (size_t)F * K;
+    tr.base = tr.heads + F;
+    tr.next_id = tr.base + F;
+    uint32_t* prev_count = tr.next_id + 1;
+    uint32_t* carry[2] = {prev_count + 1, prev_count + 1 + 2u * (size_t)K};
+    tr.w = a.w;
+    tr.h = a.h;
+    tr.npx = a.npx;
+    tr.wpr = a.wpr;
+    tr.hw = a.hw;
+    tr.nslots = a.nslots;
+    tr.wpf = a.wpf;
+    tr.bpf = a.bpf;
+    tr.K = K;
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    const size_t frame_words = (size_t)a.wpf;
+    if (state)
+        DIPS_HIP(h, hipMemcpyAsync(tr.next_id, state, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    else
+        DIPS_HIP(h, hipMemsetAsync(tr.next_id, 0, sizeof(uint32_t), s));
+    if (prev_mask) {
+        DIPS_HIP(h, hipMemcpyAsync(carry[0], state + 1, sizeof(uint32_t) * 2u * K, hipMemcpyDeviceToDevice, s));
+        // the same labels as the call that held this frame gave it: they do not depend on max_boxes
+        a.n_frames = 1;
+        a.mask = reinterpret_cast<const uint32_t*>(prev_mask);
+        a.counts = prev_count;
+        a.boxes = nullptr;
+        a.max_boxes = 0;
+        DIPS_HIP(h, dips::launch_mask_components(a, s));
+        DIPS_HIP(h, dips::launch_mask_tracks_keep(tr, a.mask, 1u, s));
+    }
+    a.max_boxes = K;
+    // the records no component fills are zeros
+    DIPS_HIP(h, hipMemsetAsync(boxes, 0, sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * K, s));
+    tr.prev0 = reinterpret_cast<const uint32_t*>(prev_mask);
+    uint32_t cin = 0;
+    for (uint32_t t = 0; t < n_frames; t += F) {
+        const uint32_t n = std::min(F, n_frames - t);
+        a.n_frames = n;
+        a.mask = reinterpret_cast<const uint32_t*>(mask) + (size_t)t * frame_words;
+        a.counts = counts + t;
+        a.boxes = boxes + (size_t)t * K * DIPS_BOX_WORDS;
+        DIPS_HIP(h, dips::launch_mask_components(a, s));
+        tr.n_frames = n;
+        tr.mask = a.mask;
+        tr.counts = a.counts;
+        tr.links = links + (size_t)t * K * DIPS_LINK_WORDS;
+        tr.carry_in = carry[cin];
+        tr.carry_out = carry[cin ^ 1u];
+        DIPS_HIP(h, dips::launch_mask_tracks(tr, s));
+        cin ^= 1u;
+        if (t + n < n_frames) {
+            tr.prev0 = a.mask + (size_t)(n - 1u) * frame_words;
+            DIPS_HIP(h, dips::launch_mask_tracks_keep(tr, tr.prev0, n, s));
+        }
+    }
+    if (state) {
+        DIPS_HIP(h, hipMemcpyAsync(state, tr.next_id, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        DIPS_HIP(h, hipMemcpyAsync(state + 1, carry[cin], sizeof(uint32_t) * 2u * K, hipMemcpyDeviceToDevice, s));
+    }
+    return span.end(s);
+}
+
+// ---------------------------------------------------------------------------
+// The binary morphology of a mask (dips_mask_morph; kernel in mask_morph.hip)
+// ---------------------------------------------------------------------------
+
+// One launch over the frames of a device mask, asynchronously on `s`.
+dips_status run_morph_device(dips_handle* h, const uint8_t* mask_in, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                             uint32_t op, uint32_t shape, uint32_t rx, uint32_t ry, uint8_t* mask_out,
+                             hipStream_t s) {
+    dips::MorphArgs a{};
+    a.in = reinterpret_cast<const uint32_t*>(mask_in);
+    a.out = reinterpret_cast<uint32_t*>(mask_out);
+    a.w = w;
+    a.h = hgt;
+    a.wpr = (uint32_t)mask_words_per_row(w);
+    a.n_frames = n_frames;
+    a.op = op;
+    a.shape = shape;
+    a.rx = rx;
+    a.ry = ry;
+    dips::mask_morph_tiling(w, hgt, &a.tiles_x, &a.tiles_y);
+    a.items = (uint64_t)n_frames * a.tiles_x * a.tiles_y;
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    DIPS_HIP(h, dips::launch_mask_morph(a, s));
+    return span.end(s);
+}
+
+}  // namespace
+
+extern "C" {
+
+dips_status dips_mask_components(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w,
+                                 uint32_t roi_h, uint32_t connectivity, uint32_t min_area, uint32_t max_boxes,
+                                 uint32_t chunk_frames, uint32_t* counts, uint32_t* boxes, uint32_t* labels) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask || !counts || (!boxes && max_boxes != 0u))
+            return fail(h, DIPS_ERR_INVALID, "mask_components: null argument");
+        DIPS_TRY(check_labelling(h, "mask_components", n_frames, roi_w, roi_h, connectivity, max_boxes));
+        const uint64_t n_px = (uint64_t)roi_w * roi_h;
+        if (max_boxes == 0u) boxes = nullptr;
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_components", {mask, counts, boxes, labels}));
+            return run_components_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
+                                         chunk_frames, counts, boxes, labels, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call); counts and
+        // boxes share one buffer
+        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const size_t counts_bytes = sizeof(uint32_t) * (size_t)n_frames;
+        const size_t boxes_bytes = sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
+        const size_t labels_bytes = labels ? sizeof(uint32_t) * (size_t)n_px * n_frames : 0u;
+        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes));
+        DIPS_HIP(h, h->stage_series.ensure(counts_bytes + boxes_bytes));
+        if (labels) DIPS_HIP(h, h->stage_map.ensure(labels_bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        uint32_t* counts_dev = h->stage_series.as<uint32_t>();
+        uint32_t* boxes_dev = max_boxes != 0u ? counts_dev + n_frames : nullptr;
+        st = run_components_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, connectivity, min_area,
+                                   max_boxes, chunk_frames, counts_dev, boxes_dev,
+                                   labels ? h->stage_map.as<uint32_t>() : nullptr, h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (max_boxes != 0u)
+            DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (labels) DIPS_HIP(h, hipMemcpyAsync(labels, h->stage_map.p, labels_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_tracks(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                             uint32_t connectivity, uint32_t min_area, uint32_t max_boxes, uint32_t chunk_frames,
+                             const uint8_t* prev_mask, uint32_t* state, uint32_t* counts, uint32_t* boxes,
+                             uint32_t* links) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask || !counts || !boxes || !links) return fail(h, DIPS_ERR_INVALID, "mask_tracks: null argument");
+        if (max_boxes == 0u || max_boxes > DIPS_TRACK_MAX_BOXES)
+            return fail(h, DIPS_ERR_INVALID, "mask_tracks: max_boxes must be 1 .. 256");
+        if (prev_mask && !state) return fail(h, DIPS_ERR_INVALID, "mask_tracks: prev_mask needs state");
+        DIPS_TRY(check_labelling(h, "mask_tracks", n_frames, roi_w, roi_h, connectivity, max_boxes));
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_tracks", {mask, prev_mask, state, counts, boxes, links}));
+            return run_tracks_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes, chunk_frames,
+                                     prev_mask, state, counts, boxes, links, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call); the frame
+        // before the clip behind the mask, the outputs and the state in one buffer
+        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        const size_t mask_bytes = frame_bytes * n_frames;
+        const size_t counts_words = (size_t)n_frames;
+        const size_t boxes_words = DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
+        const size_t links_words = DIPS_LINK_WORDS * (size_t)n_frames * max_boxes;
+        const size_t state_words = 1u + 2u * (size_t)max_boxes;
+        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes + frame_bytes));
+        DIPS_HIP(h, h->stage_series.ensure(sizeof(uint32_t) * (counts_words + boxes_words + links_words + state_words)));
+        uint8_t* mask_dev = h->stage_frames.as<uint8_t>();
+        uint8_t* prev_dev = prev_mask ? mask_dev + mask_bytes : nullptr;
+        uint32_t* counts_dev = h->stage_series.as<uint32_t>();
+        uint32_t* boxes_dev = counts_dev + counts_words;
+        uint32_t* links_dev = boxes_dev + boxes_words;
+        uint32_t* state_dev = state ? links_dev + links_words : nullptr;
+        DIPS_HIP(h, hipMemcpyAsync(mask_dev, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        if (prev_mask) DIPS_HIP(h, hipMemcpyAsync(prev_dev, prev_mask, frame_bytes, hipMemcpyHostToDevice, h->stream));
+        if (state)
+            DIPS_HIP(h, hipMemcpyAsync(state_dev, state, sizeof(uint32_t) * state_words, hipMemcpyHostToDevice, h->stream));
+        st = run_tracks_device(h, mask_dev, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes, chunk_frames,
+                               prev_dev, state_dev, counts_dev, boxes_dev, links_dev, h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, sizeof(uint32_t) * counts_words, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, sizeof(uint32_t) * boxes_words, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipMemcpyAsync(links, links_dev, sizeof(uint32_t) * links_words, hipMemcpyDeviceToHost, h->stream));
+        if (state)
+            DIPS_HIP(h, hipMemcpyAsync(state, state_dev, sizeof(uint32_t) * state_words, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_morph(dips_handle* h, const uint8_t* mask_in, uint32_t n_frames, uint32_t roi_w,
+                            uint32_t roi_h, uint32_t op, uint32_t shape, uint32_t rx, uint32_t ry,
+                            uint8_t* mask_out) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask_in || !mask_out) return fail(h, DIPS_ERR_INVALID, "mask_morph: null argument");
+        if (op > DIPS_MORPH_CLOSE) return fail(h, DIPS_ERR_INVALID, "mask_morph: op must be 0 .. 3");
+        if (shape > DIPS_MORPH_DIAMOND) return fail(h, DIPS_ERR_INVALID, "mask_morph: shape must be 0 or 1");
+        if (rx > DIPS_MORPH_MAX_RADIUS || ry > DIPS_MORPH_MAX_RADIUS)
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: rx and ry must be 0 .. 15");
+        if (shape == DIPS_MORPH_DIAMOND && ry != rx)
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: a diamond needs ry == rx");
+        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_morph: roi_w and roi_h must not be 0");
+        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: the region must stay below 2^30 pixels");
+        const size_t bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const uintptr_t pi = (uintptr_t)mask_in, po = (uintptr_t)mask_out;
+        if (pi < po + bytes && po < pi + bytes)
+            return fail(h, DIPS_ERR_INVALID, "mask_morph: mask_in and mask_out must not overlap");
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            if (((pi | po) & 3u) != 0)
+                return fail(h, DIPS_ERR_INVALID, "mask_morph: the device pointers must be 4-byte aligned");
+            return run_morph_device(h, mask_in, n_frames, roi_w, roi_h, op, shape, rx, ry, mask_out, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call)
+        DIPS_HIP(h, h->stage_frames.ensure(bytes));
+        DIPS_HIP(h, h->stage_map.ensure(bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask_in, bytes, hipMemcpyHostToDevice, h->stream));
+        st = run_morph_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, op, shape, rx, ry,
+                              h->stage_map.as<uint8_t>(), h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """Test helper: the part-major schedule the library picks for a 'per-frame'
-RGB8 / RGBA8 batch, restated from series_abi.hip part_geometry so that a test
+RGB8 / RGBA8 batch, restated from series_sched.h part_geometry so that a test
 can assert which schedule a launch runs (and that the library agrees: the
 wave count it reports must equal the restatement's)."""
 from __future__ import annotations

@@ -104,7 +104,8 @@ def test_every_exported_function_body_is_inside_the_guard():
         if where == "dips_abi::CommCreateTag{}":
             assert name.startswith(("dips_comm_create", "dips_comm_unique_id")), name
     # the guard's translation units use the guard from abi_guard.h
-    for fn in ("dips_abi.hip", "compat_abi.hip", "series_abi.hip", "alt_abi.hip", "shard_abi.hip"):
+    for fn in ("dips_abi.hip", "compat_abi.hip", "series_abi.hip", "region_abi.hip", "mask_abi.hip", "alt_abi.hip",
+               "shard_abi.hip"):
         assert "using dips_abi::guard;" in sources[fn], fn
 
 

@@ -8,7 +8,7 @@ the reference alone: at tau > 0 its mask from frame 1 on has 5-95 % of its
 bits set; on the drift clip at k = 1 .. 3 it differs from both the
 'per-frame' and the 'overall' oracle mask in at least 5 % of the bits.
 
-Schedule (series_abi.hip background_geometry): one part always; a tile is 64
+Schedule (series_sched.h background_geometry): one part always; a tile is 64
 * kUnrollBackground vecs of the region rows padded to whole mask words, 64
 vecs when the larger tiles would fill under half of the wave slots (every
 small shape here; test_large_tiles reaches the larger tiles)."""

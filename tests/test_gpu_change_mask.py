@@ -7,7 +7,7 @@ tau > 0 case asserts that the oracle's mask has 20-80 % of its bits set, every
 tau = 0 case that it has zeros and ones.  Every comparison is np.array_equal
 on the whole mask, pad bits included.
 
-Schedule (series_abi.hip mask_geometry): a tile is 64 * kUnrollMask vecs of
+Schedule (series_sched.h mask_geometry): a tile is 64 * kUnrollMask vecs of
 the region rows padded to whole mask words; the frames are cut into as many
 parts of >= 16 frames as give every wave slot (4 waves per SIMD x 4 SIMDs x
 the CUs, far more than the tiles of any small shape here) an item: one part

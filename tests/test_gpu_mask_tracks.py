@@ -247,6 +247,27 @@ def test_host_pointers_against_device_pointers(op):
     same(got_host, want(mask, w, connectivity, min_area, K))
 
 
+def test_kernel_time_has_one_entry_per_call():
+    import torch
+    from dips_amd import DiffSeriesOperator, Mode, PixelFormat
+    K = 8
+    mask = cref.pack(random_bits(7, 33, 65, 0.45))
+    ref_counts = want(mask, 65, max_boxes=K)[0]
+    mask_dev = torch.from_numpy(mask).cuda()
+    state = torch.zeros((1 + 2 * K,), dtype=torch.int32, device="cuda")
+    o = DiffSeriesOperator(PixelFormat.RGB8, Mode.PerFrame, 8 / 255, time_kernel=True)
+    try:
+        one = _device_call(o, mask_dev, 65, K, 8, 1)[0]                                       # one chunk
+        four = _device_call(o, mask_dev, 65, K, 8, 1, chunk_frames=2)[0]                      # four chunks
+        carried = _device_call(o, mask_dev[1:], 65, K, 8, 1, prev=mask_dev[0], state=state)[0]  # a labelled predecessor
+        ms, launches = o.kernel_time()
+        each = o.kernel_times()
+    finally:
+        o.close()
+    assert launches == 3 and len(each) == 3 and ms > 0.0 and all(t > 0.0 for t in each)
+    assert np.array_equal(one, ref_counts) and np.array_equal(four, ref_counts) and np.array_equal(carried, ref_counts[1:])
+
+
 # -- refused arguments ----------------------------------------------------------------
 
 def test_refused_arguments_leave_the_outputs_untouched(op):

@@ -1,7 +1,7 @@
 """The largest frames, on both sides of the vectorised kernels' limit: a
 frame of 2^31 bytes or more (the kernels' 32-bit frame offsets) goes to the
 generic kernel with 64-bit offsets, one just under it to the vectorised
-kernel (series_abi.hip fast_geometry / gray_lut_geometry)."""
+kernel (series_sched.h fast_geometry / gray_lut_geometry)."""
 import numpy as np
 import pytest
 

@@ -7,7 +7,7 @@ Frames are independent random bytes unless stated (small-noise video has count
 random frames asserts that the threshold bites.  All comparisons are
 np.array_equal.
 
-Schedules (series_abi.hip pix_geometry; 4 waves per SIMD x 4 SIMDs x the CUs
+Schedules (series_sched.h pix_geometry; 4 waves per SIMD x 4 SIMDs x the CUs
 wave slots, far more than the tiles of any shape here): one part -- plain
 stores, or load-add-store when accumulating -- for fewer than 32 frames (9
 and 5 frames: every 37x29, 96x64x9 and 1280x720 case); frames in parts added

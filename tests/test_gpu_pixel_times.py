@@ -8,7 +8,7 @@ pixel to pixel; every case asserts check_informative on the oracle's planes
 and the part cases that at least 10 % of the pixels have a run that crosses a
 part boundary.  Every comparison is np.array_equal on all four planes.
 
-Schedule (series_abi.hip times_geometry): a tile is 64 * kUnrollTimes vecs of
+Schedule (series_sched.h times_geometry): a tile is 64 * kUnrollTimes vecs of
 the region; tiles that fill less than 98 % of the wave slots are cut into
 parts of >= 16 frames (one part below 32 frames, parts of 19 and 18 at 37
 frames, of 17 at 300 frames); DIPS_PIXEL_PART_FRAMES pins the part length.

@@ -592,7 +592,7 @@ def test_4k_forms_agree_and_match_oracle(mode):
                                              ("Gray8", 2048, 1536, 1000)])
 def test_part_major_schedule_matches_contiguous_and_oracle(fmt_name, w, h, n):
     """'Per-frame' batches of >= 256 frames run the part-major schedule
-    (series_abi.hip part_geometry; series_v2.hip / series_gray.hip item loop).
+    (series_sched.h part_geometry; series_v2.hip / series_gray.hip item loop).
     These shapes take it on a 256-CU MI355X: 1080p RGB8 4 parts of 131
     frames (the last 130), RGBA8 4 parts of 132 (the last 129), 2048x1536
     gray8 7 parts of 143 (the last 142), so items start mid-batch, segments

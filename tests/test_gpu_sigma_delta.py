@@ -6,7 +6,7 @@ per frame) and the drift-and-moving-square clip.  Informative-input conditions
 are asserted on the reference alone: its mask from frame 1 on has 5-95 % of
 its bits set, and where stated V takes at least 3 distinct values.
 
-Schedule (series_abi.hip background_geometry with the Sigma-Delta kernels):
+Schedule (series_sched.h background_geometry with the Sigma-Delta kernels):
 one part always; a tile is 64 * kUnrollSigmaDelta vecs of the region rows
 padded to whole mask words, 64 vecs when the larger tiles would fill under
 half of the wave slots (every small shape here; test_large_tiles reaches the

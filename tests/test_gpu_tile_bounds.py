@@ -4,7 +4,7 @@ oracle.  A tile is one wave's slice of a frame: 64 lanes x U vecs of 4 px --
 for the GRAY8 table kernel -- and the pixels past the last whole vec go to
 the generic kernel.  Each size runs in both modes, with the u8 map, in
 batches of 7 and 260 frames (frames this small keep one contiguous range
-per wave); the part-major schedule (series_abi.hip part_geometry) with a
+per wave); the part-major schedule (series_sched.h part_geometry) with a
 partial last tile is the second test."""
 import numpy as np
 import pytest

@@ -3,7 +3,7 @@ frame (BASELINE.json configs[2]: 3840x2160 RGB8, 'per-frame', tau = 8/255,
 the default intensity-sum form ISI = 1 -- series_v2_kernel<3, 0, 5, true,
 false, false, 1>).
 
-The bench's 5000-frame batch runs the part-major schedule (series_abi.hip
+The bench's 5000-frame batch runs the part-major schedule (series_sched.h
 part_geometry: 5 parts of 1000 frames); a 520-frame batch of the same frames
 runs it with 3 parts of 174 frames (the last 172) on a 256-CU MI355X, so
 items start mid-batch and the last part is short -- asserted through the

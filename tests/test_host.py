@@ -284,7 +284,7 @@ def test_pack_frame_for_the_zero_copy_input(tmp_path):
 def test_bench_kernel_name_matches_library_choice():
     """bench.py names the series_v2 instantiation the library runs, spelled
     as rocprofv3 prints it (ISI an int): run_series_device's choice of the
-    intensity-sum form (series_abi.hip series_isi_form)."""
+    intensity-sum form (series_host.h series_isi_form)."""
     import bench
     assert bench._v2_kernel_name(True, 8 / 255) == "series_v2_kernel<3, 0, 5, true, false, false, 1>"
     assert bench._v2_kernel_name(False, 8 / 255, with_map=True) == "series_v2_kernel<3, 0, 5, false, true, false, 1>"

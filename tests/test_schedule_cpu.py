@@ -1,5 +1,5 @@
 """The part-major schedule restatement used by the GPU tests (tests/_sched.py)
-against the figures dips_abi.hip part_geometry documents: the bench's 4K
+against the figures series_sched.h part_geometry documents: the bench's 4K
 batch, the 1080p part-major parity shape, and the shapes the new GPU tests
 rely on (256-CU MI355X; the RGB8 kernel's 5 vecs per lane run 4 waves per
 SIMD)."""
