@@ -7,7 +7,7 @@ dips/src/gpu/mod.rs) plus the batch difference-series operator and the
 frame-range sharding over RCCL (dips_amd.shard).
 """
 from . import alt  # dips_alt crate surface (DiPsCompute, run_dips_on_file loop)
-from ._lib import DipsError, DipsLibraryError, LIB_PATH, load as load_library
+from ._lib import DipsError, DipsLibraryError, LIB_PATH, VOTE_MAX_WINDOW, load as load_library
 from .api import (Background, ChangeBoxes, ChangeMask, ChangeTracks, ChromaFilter, ComputeState, DiffSeriesOperator, DiPsFilter, DiPsProperties,
                   FrameCallbackNotSpecifiedError, GridSeries, Mode, MorphOp, MorphShape, PixelFormat, PixelSums, PixelTimes, Series,
                   SigmaDelta, VideoPathNotSpecifiedError, diff_series, frame_callback, grid_cell, mask_row_bytes,
@@ -16,6 +16,6 @@ from .api import (Background, ChangeBoxes, ChangeMask, ChangeTracks, ChromaFilte
 __all__ = [
     "Background", "ChangeBoxes", "ChangeMask", "ChangeTracks", "ChromaFilter", "ComputeState", "DiffSeriesOperator", "DiPsFilter", "DiPsProperties",
     "DipsError", "DipsLibraryError", "FrameCallbackNotSpecifiedError", "GridSeries", "LIB_PATH", "Mode", "MorphOp", "MorphShape",
-    "PixelFormat", "PixelSums", "PixelTimes", "Series", "SigmaDelta", "VideoPathNotSpecifiedError", "diff_series", "frame_callback", "grid_cell",
+    "PixelFormat", "PixelSums", "PixelTimes", "Series", "SigmaDelta", "VOTE_MAX_WINDOW", "VideoPathNotSpecifiedError", "diff_series", "frame_callback", "grid_cell",
     "load_library", "mask_row_bytes", "perform_dips_frames", "si_from_fixed",
 ]

@@ -51,6 +51,7 @@ TRACK_MAX_BOXES = 256  # DIPS_TRACK_MAX_BOXES
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # DIPS_MORPH_ERODE .. DIPS_MORPH_CLOSE
 MORPH_BOX, MORPH_DIAMOND = 0, 1  # DIPS_MORPH_BOX, DIPS_MORPH_DIAMOND
 MORPH_MAX_RADIUS = 15  # DIPS_MORPH_MAX_RADIUS
+VOTE_MAX_WINDOW = 31  # DIPS_VOTE_MAX_WINDOW
 BG_SELECTIVE = 1  # DIPS_BG_SELECTIVE
 BG_MAX_RATE_SHIFT = 8  # DIPS_BG_MAX_RATE_SHIFT
 SD_MAX_AMP = 15  # DIPS_SD_MAX_AMP
@@ -204,6 +205,7 @@ def load() -> ctypes.CDLL:
             "dips_mask_components": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _vp, _vp, _vp], st),
             "dips_mask_tracks": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, _vp, _vp, _vp, _vp], st),
             "dips_mask_morph": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p], st),
+            "dips_mask_vote": ([_vp, _u8p, u32, u32, u32, u32, u32, _u8p, _u8p, _u8p], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),
             "dips_diff_series_streamed": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, u32], st),
             "dips_synth_frames": ([_vp, u32, u32, u64, u64, u32, _u8p], st),

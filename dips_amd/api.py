@@ -762,6 +762,27 @@ def _morph_steps(morph, w: int, h: int) -> List[Tuple[int, int, int, int]]:
     return steps
 
 
+def _vote_args(window, votes=None) -> Tuple[int, int]:
+    """(window, votes) of dips_mask_vote, checked; votes None means the
+    majority, window // 2 + 1."""
+    window = int(window)
+    if not 1 <= window <= _lib.VOTE_MAX_WINDOW:
+        raise ValueError(f"window must be 1 .. {_lib.VOTE_MAX_WINDOW}")
+    votes = window // 2 + 1 if votes is None else int(votes)
+    if not 1 <= votes <= window:
+        raise ValueError("votes must be 1 .. window")
+    return window, votes
+
+
+def _vote_option(vote) -> Tuple[int, int]:
+    """change_boxes' vote: window or (window, votes), checked."""
+    if isinstance(vote, (tuple, list)):
+        if len(vote) != 2:
+            raise ValueError("vote must be window or (window, votes)")
+        return _vote_args(vote[0], vote[1])
+    return _vote_args(vote)
+
+
 def _roi_arg(roi):
     """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
     if roi is None:
@@ -1386,10 +1407,91 @@ class DiffSeriesOperator:
                 self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, op, shape, rx, ry,
                 out.data_ptr() if n else None))
 
-    def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args, sigma_delta=None):
+    # -- the temporal m-of-k vote on a change mask (dips_mask_vote) ------------
+    def mask_vote(self, mask: ChangeMask, window: int = 3, votes: Optional[int] = None,
+                  history: Optional[ChangeMask] = None) -> Tuple[ChangeMask, ChangeMask]:
+        """(voted, next_history): bit (t, y, x) of `voted` is set when at
+        least `votes` of the `window` frames t - window + 1 .. t of `mask`
+        have it set (votes None: the majority, window // 2 + 1; 1: the OR,
+        window: the AND of the window).  The frames before the clip are the
+        window - 1 frames of `history`, oldest first (None: clear).
+        next_history, the last window - 1 frames of history and mask
+        together, continues a clip in a later call: chunk by chunk gives
+        what one call over the whole clip gives.  A mask that lives on the
+        device goes through run_mask_vote_device."""
+        if not isinstance(mask, ChangeMask) or (history is not None and not isinstance(history, ChangeMask)):
+            raise ValueError("mask and history must be ChangeMasks")
+        window, votes = _vote_args(window, votes)
+        bits = np.ascontiguousarray(mask.bits, dtype=np.uint8)
+        rw = int(mask.width)
+        if bits.ndim != 3 or rw <= 0 or bits.shape[1] == 0 or bits.shape[2] != 4 * ((rw + 31) // 32):
+            raise ValueError("mask.bits must be [n, h, 4 * ceil(width / 32)] bytes, h and width not 0")
+        n, rh = int(bits.shape[0]), int(bits.shape[1])
+        if rw * rh >= 1 << 30:
+            raise ValueError("the region must stay below 2^30 pixels")
+        hist = None
+        if history is not None and window > 1:
+            hist = np.ascontiguousarray(history.bits, dtype=np.uint8)
+            if int(history.width) != rw or hist.shape != (window - 1, rh, bits.shape[2]):
+                raise ValueError("history must hold window - 1 frames of the mask's region")
+        out = np.zeros_like(bits)
+        nxt = np.zeros((window - 1, rh, bits.shape[2]), dtype=np.uint8)
+        self._host.check(self._host._lib.dips_mask_vote(
+            self._host.ptr, bits.ctypes.data if n else None, n, rw, rh, window, votes,
+            hist.ctypes.data if hist is not None else None, nxt.ctypes.data if window > 1 else None,
+            out.ctypes.data if n else None))
+        return ChangeMask(out, rw), ChangeMask(nxt, rw)
+
+    def run_mask_vote_device(self, mask, width: int, out, window: int = 3, votes: Optional[int] = None,
+                             history=None, history_out=None, stream=None) -> None:
+        """Asynchronous: mask and out uint8 device tensors [N, h, row_bytes]
+        as run_change_mask_device writes them for a region `width` pixels
+        wide, history and history_out (either may be None) such tensors of
+        window - 1 frames; all 4-byte aligned, no output overlapping an input
+        or the other output.  Every byte of out and history_out is written."""
+        import torch
+        rw = int(width)
+        window, votes = _vote_args(window, votes)
+        if window == 1:
+            history = history_out = None
+        given = [t for t in (mask, out, history, history_out) if t is not None]
+        for t in given:
+            if t.dim() != 3 or rw <= 0 or t.shape[2] != 4 * ((rw + 31) // 32) or t.dtype != torch.uint8:
+                raise ValueError("the masks must be uint8 tensors of shape [N, h, 4 * ceil(width / 32)]")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device path needs contiguous HIP tensors")
+        if tuple(out.shape) != tuple(mask.shape):
+            raise ValueError("out must have the shape of mask")
+        n, rh = int(mask.shape[0]), int(mask.shape[1])
+        if rh == 0:
+            raise ValueError("the mask's height must not be 0")
+        if rw * rh >= 1 << 30:
+            raise ValueError("the region must stay below 2^30 pixels")
+        for t in (history, history_out):
+            if t is not None and tuple(t.shape) != (window - 1, rh, int(mask.shape[2])):
+                raise ValueError("history and history_out must hold window - 1 frames of the mask's region")
+
+        def overlap(a, b):
+            return (a is not None and b is not None and a.numel() and b.numel()
+                    and a.data_ptr() < b.data_ptr() + b.numel() and b.data_ptr() < a.data_ptr() + a.numel())
+
+        if (overlap(out, mask) or overlap(out, history) or overlap(history_out, mask)
+                or overlap(history_out, history) or overlap(out, history_out)):
+            raise ValueError("an output must not overlap an input or the other output")
+        if any(t.numel() and (t.data_ptr() & 3) != 0 for t in given):
+            raise ValueError("the masks must be 4-byte aligned")
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_vote(
+                self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, window, votes,
+                history.data_ptr() if history is not None else None,
+                history_out.data_ptr() if history_out is not None else None,
+                out.data_ptr() if n else None))
+
+    def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args, sigma_delta=None, vote=None):
         """(mask, region width, region height, n): the change mask of
-        change_boxes / change_tracks as a device tensor, behind its morph
-        steps; check_args(n) runs once the geometry is known."""
+        change_boxes / change_tracks as a device tensor, behind its vote and
+        its morph steps; check_args(n) runs once the geometry is known."""
         import torch
         if sigma_delta is not None and background is not None:
             raise ValueError("sigma_delta and background exclude each other")
@@ -1406,6 +1508,7 @@ class DiffSeriesOperator:
         rh, rw = self._region(roi, h, w)
         check_args(n)
         steps = _morph_steps(morph, rw, rh) if morph is not None else []
+        vote = _vote_option(vote) if vote is not None else None
         if background is not None:
             bg_k, bg_sel = background if isinstance(background, (tuple, list)) else (background, False)
             _background_args(bg_k, bg_sel)
@@ -1424,8 +1527,11 @@ class DiffSeriesOperator:
         else:
             bg = torch.empty((int(self.fmt), rh, rw), dtype=torch.int16, device=dev)
             self.run_background_mask_device(frames, bg, mask, roi=roi, ref=ref, rate_shift=bg_k, selective=bg_sel)
+        other = torch.empty_like(mask) if steps or vote is not None else None
+        if vote is not None:  # one-shot: clear frames before the clip, no history kept
+            self.run_mask_vote_device(mask, rw, other, vote[0], vote[1])
+            mask, other = other, mask
         if steps:
-            other = torch.empty_like(mask)
             for op_, shape_, rx_, ry_ in steps:  # ping-pong: the newest mask is `mask`
                 self.run_mask_morph_device(mask, rw, other, op_, rx_, ry_, shape_)
                 mask, other = other, mask
@@ -1433,7 +1539,7 @@ class DiffSeriesOperator:
 
     def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
                      max_boxes: int = 64, labels: bool = False, morph=None, background=None,
-                     sigma_delta=None) -> ChangeBoxes:
+                     sigma_delta=None, vote=None) -> ChangeBoxes:
         """change_mask, then mask_components, with the mask kept on the
         device between the two: the moving objects of every frame.  frames /
         ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
@@ -1443,11 +1549,14 @@ class DiffSeriesOperator:
         the mask against the running-average background (background_mask)
         instead of the operator's mode.  sigma_delta: None, or True or
         (n_amp, v_min, v_max) to take the mask under the Sigma-Delta model's
-        per-pixel threshold (sigma_delta_mask); it excludes background."""
+        per-pixel threshold (sigma_delta_mask); it excludes background.
+        vote: None, or window or (window, votes) of mask_vote, applied to
+        the model's mask before the morph steps with clear frames before the
+        clip (the call is one-shot: no history is carried)."""
         import torch
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
-            lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta)
+            lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta, vote)
         dev, k = mask.device, int(max_boxes)
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
@@ -1460,7 +1569,8 @@ class DiffSeriesOperator:
         return ChangeBoxes(to_u32(counts), to_u32(boxes), to_u32(lab) if lab is not None else None)
 
     def change_tracks(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
-                      max_boxes: int = 64, morph=None, background=None, sigma_delta=None) -> ChangeTracks:
+                      max_boxes: int = 64, morph=None, background=None, sigma_delta=None,
+                      vote=None) -> ChangeTracks:
         """change_mask, then mask_tracks, with the mask kept on the device
         between the two: the moving objects of every frame and their
         identity from frame to frame.  The arguments are change_boxes'; the
@@ -1468,7 +1578,7 @@ class DiffSeriesOperator:
         import torch
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
-            lambda n_: _tracks_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta)
+            lambda n_: _tracks_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta, vote)
         dev, k = mask.device, int(max_boxes)
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)

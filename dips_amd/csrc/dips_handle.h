@@ -7,7 +7,7 @@
 //   series_abi.hip  the north-star difference series and its measurement legs
 //   region_abi.hip  the regional products: grid, pixel sums, change mask,
 //                   pixel times, background and Sigma-Delta models
-//   mask_abi.hip    the mask products: components, tracks, morphology
+//   mask_abi.hip    the mask products: components, tracks, morphology, vote
 //   shard_abi.hip   the frame-range sharding of the series
 // (series_host.h: what the series, region and mask units share; series_sched.h:
 // their schedules as functions of plain numbers.)

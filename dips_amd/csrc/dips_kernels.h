@@ -416,6 +416,33 @@ struct MorphArgs {
     uint32_t tiles_y;
 };
 
+// The temporal m-of-k vote on a batch of change-mask frames (mask_vote.hip):
+// one launch over items (frame part, tile of 64 * kVoteWords words), and one
+// over the window - 1 frames of the next history.
+// Mask words a lane owns.  Measured at 4K, 500 frames: 1 word fills
+// the wave slots at every window and is as fast as 2 at k = 3 and 1.4x faster
+// at k = 31, where 2 words leave half the slots empty; 4 words spill.
+#ifndef DIPS_VOTE_WORDS
+#define DIPS_VOTE_WORDS 1
+#endif
+constexpr int kVoteWords = DIPS_VOTE_WORDS;
+struct VoteArgs {
+    const uint32_t* in;       // n_frames frames of wpf words (may be NULL when n_frames == 0)
+    const uint32_t* hist_in;  // window - 1 frames before the clip, oldest first; NULL: all clear
+    uint32_t* out;            // n_frames frames; every word is written, pad bits 0
+    uint32_t* hist_out;       // window - 1 frames (launch_mask_vote_history only)
+    uint32_t w;
+    uint32_t wpr;             // mask words per row
+    uint32_t wpf;             // mask words per frame, < 2^30
+    uint32_t n_frames;
+    uint32_t window;          // k, 1 .. DIPS_VOTE_MAX_WINDOW
+    uint32_t votes;           // m, 1 .. k
+    uint32_t part_frames;     // from vote_geometry
+    uint32_t parts;
+    uint32_t n_tiles;
+    uint32_t n_waves;
+};
+
 struct SynthArgs {
     uint8_t* dst;
     uint64_t total_bytes;
@@ -638,6 +665,12 @@ hipError_t launch_mask_tracks_keep(const TracksArgs& a, const uint32_t* frame, u
 // call on `s`, and the tiles it cuts a w x h frame into
 hipError_t launch_mask_morph(const MorphArgs& a, hipStream_t s);
 void mask_morph_tiling(uint32_t w, uint32_t h, uint32_t* tiles_x, uint32_t* tiles_y);
+// the temporal vote on mask frames (mask_vote.hip): the launch over the
+// frames of a call on `s` (`blocks` of 4 waves), and the one that writes the
+// next history (any n_frames, 0 included)
+const void* mask_vote_kernel_ptr();
+hipError_t launch_mask_vote(const VoteArgs& a, uint32_t blocks, hipStream_t s);
+hipError_t launch_mask_vote_history(const VoteArgs& a, hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 hipError_t launch_read_ceiling(const uint8_t* p, uint64_t bytes, uint32_t* out, hipStream_t s);
 // read-only walk in the RGB8 / RGBA8 series kernel's shape (vec_bytes 12 / 16, U = kUnrollV2Rgb / kUnrollV2)

@@ -57,6 +57,11 @@
 //            applied in the order given; --mask then writes the cleaned mask
 //            and --boxes / --tracks take the components of the cleaned mask, and the
 //            stdout line ends with morph=<steps>
+//            [--vote K[,M]] -> with --mask, --boxes or --tracks: the temporal
+//            M-of-K vote on the change mask with dips_mask_vote (K 1 .. 31, M
+//            1 .. K, default the majority K / 2 + 1), over the whole clip in
+//            one call with clear frames before it, applied before --morph;
+//            the stdout line has vote=K,M; a bad value exits with status 2
 //            [--background K[,selective] [--background-out FILE]] -> with
 //            --mask, --boxes or --tracks: the mask is taken against the running-average
 //            background with dips_diff_background_mask (rate_shift K in
@@ -139,6 +144,7 @@ int usage() {
                  "                [--mask FILE [--roi x,y,w,h]] [--pixel-times FILE [--roi x,y,w,h]]\n"
                  "                [--boxes FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
                  "                [--tracks FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
+                 "                [--vote K[,M]] (with --mask, --boxes or --tracks; before --morph)\n"
                  "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask, --boxes or --tracks)\n"
                  "                [--background K[,selective] [--background-out FILE]] (with --mask, --boxes or --tracks)\n"
                  "                [--sigma-delta N[,VMIN[,VMAX]] [--sigma-delta-out FILE]] (likewise; not with --background)\n"
@@ -284,6 +290,30 @@ int write_background(const BackgroundOpt& bg, const SigmaDeltaOpt& sd, const std
 void print_background(const BackgroundOpt& bg, const SigmaDeltaOpt& sd) {
     if (bg.on) std::printf(" background=%u%s", bg.rate_shift, bg.flags ? ",selective" : "");
     if (sd.on) std::printf(" sigma_delta=%u,%u,%u", sd.n_amp, sd.v_min, sd.v_max);
+}
+
+// --vote: window and votes of dips_mask_vote (window 0: no vote).
+struct VoteOpt {
+    uint32_t window = 0, votes = 0;
+};
+
+// "K[,M]" -> the option (K 1 .. DIPS_VOTE_MAX_WINDOW, M 1 .. K, default K / 2 + 1)
+bool parse_vote(const std::string& s, VoteOpt* v) {
+    const size_t comma = s.find(',');
+    if (!parse_u32(s.substr(0, comma).c_str(), &v->window)) return false;
+    v->votes = v->window / 2u + 1u;
+    if (comma != std::string::npos && !parse_u32(s.substr(comma + 1).c_str(), &v->votes)) return false;
+    return v->window >= 1u && v->window <= DIPS_VOTE_MAX_WINDOW && v->votes >= 1u && v->votes <= v->window;
+}
+
+// The vote over the whole host mask of n frames of rw x rh pixels, clear
+// frames before it; the result is in `mask` again.
+int apply_vote(dips_handle* hd, std::vector<uint8_t>& mask, uint32_t n, uint32_t rw, uint32_t rh, const VoteOpt& v) {
+    if (v.window == 0u) return DIPS_OK;
+    std::vector<uint8_t> other(mask.size());
+    const int st = dips_mask_vote(hd, mask.data(), n, rw, rh, v.window, v.votes, nullptr, nullptr, other.data());
+    if (st == DIPS_OK) mask.swap(other);
+    return st;
 }
 
 // The steps in order on the host mask of n frames of rw x rh pixels; the
@@ -576,6 +606,7 @@ int run_series(int argc, char** argv) {
     uint32_t connectivity = 8, min_area = 1, max_boxes = 64;
     bool has_box_opt = false;
     std::vector<MorphStep> morph;
+    VoteOpt vote;
     BackgroundOpt bg;
     SigmaDeltaOpt sd;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
@@ -615,6 +646,11 @@ int run_series(int argc, char** argv) {
             MorphStep m{};
             if (!parse_morph(argv[++i], &m)) return usage();
             morph.push_back(m);
+        } else if (a == "--vote" && has) {
+            if (!parse_vote(argv[++i], &vote)) {  // a bad value: the status of a call the library refuses
+                usage();
+                return 2;
+            }
         } else if (a == "--background" && has) {
             if (!parse_background(argv[++i], &bg)) return usage();
         } else if (a == "--background-out" && has) {
@@ -632,6 +668,8 @@ int run_series(int argc, char** argv) {
     }
     // --morph belongs to --mask, --boxes or --tracks
     if (!morph.empty() && !mask_path && !boxes_path && !tracks_path) return usage();
+    // so does --vote
+    if (vote.window != 0u && !mask_path && !boxes_path && !tracks_path) return usage();
     // --background belongs to --mask, --boxes or --tracks, --background-out to --background
     if ((bg.on && !mask_path && !boxes_path && !tracks_path) || (bg.out_path && !bg.on)) return usage();
     // so does --sigma-delta, --sigma-delta-out to --sigma-delta; the two models exclude each other
@@ -718,6 +756,10 @@ int run_series(int argc, char** argv) {
         std::vector<uint16_t> state(state_values(sane, bg, sd, p.format, rw, rh));
         const char* what = nullptr;
         st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, sd, state, mask.data(), &what);
+        if (st == DIPS_OK && vote.window != 0u) {
+            what = "dips_mask_vote";
+            st = apply_vote(hd, mask, n, rw, rh, vote);
+        }
         if (st == DIPS_OK && !morph.empty()) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
@@ -740,6 +782,7 @@ int run_series(int argc, char** argv) {
         for (const uint8_t b : mask) set += (unsigned long long)__builtin_popcount(b);
         std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu", has_roi ? roi[0] : 0u,
                     has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
+        if (vote.window != 0u) std::printf(" vote=%u,%u", vote.window, vote.votes);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
         print_background(bg, sd);
         std::printf("\n");
@@ -763,6 +806,10 @@ int run_series(int argc, char** argv) {
         std::vector<uint16_t> state(state_values(sane, bg, sd, p.format, rw, rh));
         const char* what = nullptr;
         st = region_mask(hd, w, h, in.p, n, has_roi ? roi : nullptr, bg, sd, state, mask.data(), &what);
+        if (st == DIPS_OK && vote.window != 0u) {
+            what = "dips_mask_vote";
+            st = apply_vote(hd, mask, n, rw, rh, vote);
+        }
         if (st == DIPS_OK && !morph.empty()) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
@@ -813,6 +860,7 @@ int run_series(int argc, char** argv) {
                     tracks ? "tracks" : "boxes", has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, connectivity,
                     min_area, max_boxes, total, stored);
         if (tracks) std::printf(" tracks=%u", ids[0]);
+        if (vote.window != 0u) std::printf(" vote=%u,%u", vote.window, vote.votes);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
         print_background(bg, sd);
         std::printf("\n");

@@ -1,8 +1,8 @@
 // mask_abi.hip -- host side of include/dips_hip.h, part 5: the products of a
 // packed change mask -- its connected components, the components linked
-// across frames (tracks) and the binary morphology.  What they share with
-// the series and the regional products is in series_host.h.  Every
-// extern "C" body runs inside dips_abi::guard (abi_guard.h).
+// across frames (tracks), the binary morphology and the temporal vote.  What
+// they share with the series and the regional products is in series_host.h.
+// Every extern "C" body runs inside dips_abi::guard (abi_guard.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -250,6 +250,47 @@ dips_status run_morph_device(dips_handle* h, const uint8_t* mask_in, uint32_t n_
     return span.end(s);
 }
 
+// ---------------------------------------------------------------------------
+// The temporal m-of-k vote on a mask (dips_mask_vote; kernels in
+// mask_vote.hip)
+// ---------------------------------------------------------------------------
+
+// The vote over the frames of a device mask and the next history, each one
+// launch, asynchronously on `s`.  hist_in NULL: clear frames before the clip;
+// hist_out NULL: no next history.  n_frames may be 0 (then only the history).
+dips_status run_vote_device(dips_handle* h, const uint8_t* mask_in, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                            uint32_t window, uint32_t votes, const uint8_t* hist_in, uint8_t* hist_out,
+                            uint8_t* mask_out, hipStream_t s) {
+    dips::VoteArgs a{};
+    a.in = reinterpret_cast<const uint32_t*>(mask_in);
+    a.hist_in = reinterpret_cast<const uint32_t*>(hist_in);
+    a.out = reinterpret_cast<uint32_t*>(mask_out);
+    a.hist_out = reinterpret_cast<uint32_t*>(hist_out);
+    a.w = w;
+    a.wpr = (uint32_t)mask_words_per_row(w);
+    a.wpf = a.wpr * hgt;
+    a.n_frames = n_frames;
+    a.window = window;
+    a.votes = votes;
+    dips_sched::Geom q;
+    if (n_frames != 0) {
+        q = dips_sched::vote_geometry(a.wpf, n_frames, window, dips::kVoteWords,
+                                      resident_waves(h, dips::mask_vote_kernel_ptr()));
+        if (!q.ok) return fail(h, DIPS_ERR_HIP, "mask_vote: no schedule for this mask");
+        a.part_frames = q.part_frames;
+        a.parts = q.parts;
+        a.n_tiles = (uint32_t)q.n_tiles;
+        a.n_waves = (uint32_t)q.n_waves;
+    }
+    if (n_frames == 0 && !hist_out) return DIPS_OK;
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    if (n_frames != 0) DIPS_HIP(h, dips::launch_mask_vote(a, (uint32_t)q.blocks, s));
+    if (hist_out) DIPS_HIP(h, dips::launch_mask_vote_history(a, s));
+    return span.end(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -381,6 +422,59 @@ dips_status dips_mask_morph(dips_handle* h, const uint8_t* mask_in, uint32_t n_f
                               h->stage_map.as<uint8_t>(), h->stream);
         if (st != DIPS_OK) return st;
         DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_vote(dips_handle* h, const uint8_t* mask_in, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                           uint32_t window, uint32_t votes, const uint8_t* history_in, uint8_t* history_out,
+                           uint8_t* mask_out) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (window == 0u || window > DIPS_VOTE_MAX_WINDOW) return fail(h, DIPS_ERR_INVALID, "mask_vote: window must be 1 .. 31");
+        if (votes == 0u || votes > window) return fail(h, DIPS_ERR_INVALID, "mask_vote: votes must be 1 .. window");
+        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_vote: roi_w and roi_h must not be 0");
+        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_vote: the region must stay below 2^30 pixels");
+        if (n_frames >= (1u << 31)) return fail(h, DIPS_ERR_INVALID, "mask_vote: n_frames must stay below 2^31");
+        if (n_frames != 0 && (!mask_in || !mask_out)) return fail(h, DIPS_ERR_INVALID, "mask_vote: null argument");
+        if (window == 1u) history_in = history_out = nullptr;  // there is no history
+        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        const size_t bytes = frame_bytes * n_frames, hist_bytes = frame_bytes * (window - 1u);
+        // no output may share a byte with an input or with the other output
+        const auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+            const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+            return a && b && na != 0 && nb != 0 && pa < pb + nb && pb < pa + na;
+        };
+        if (overlap(mask_out, bytes, mask_in, bytes) || overlap(mask_out, bytes, history_in, hist_bytes) ||
+            overlap(history_out, hist_bytes, mask_in, bytes) || overlap(history_out, hist_bytes, history_in, hist_bytes) ||
+            overlap(mask_out, bytes, history_out, hist_bytes))
+            return fail(h, DIPS_ERR_INVALID, "mask_vote: an output must not overlap an input or the other output");
+        if (n_frames == 0) mask_in = mask_out = nullptr;
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_vote", {mask_in, mask_out, history_in, history_out}));
+            return run_vote_device(h, mask_in, n_frames, roi_w, roi_h, window, votes, history_in, history_out, mask_out,
+                                   h->stream);
+        }
+        if (n_frames == 0 && !history_out) return DIPS_OK;
+        // host pointers: stage through HBM (synchronous call); the history
+        // behind the mask, in and out alike
+        DIPS_HIP(h, h->stage_frames.ensure(bytes + hist_bytes));
+        DIPS_HIP(h, h->stage_map.ensure(bytes + hist_bytes));
+        uint8_t* in_dev = h->stage_frames.as<uint8_t>();
+        uint8_t* out_dev = h->stage_map.as<uint8_t>();
+        if (bytes) DIPS_HIP(h, hipMemcpyAsync(in_dev, mask_in, bytes, hipMemcpyHostToDevice, h->stream));
+        if (history_in)
+            DIPS_HIP(h, hipMemcpyAsync(in_dev + bytes, history_in, hist_bytes, hipMemcpyHostToDevice, h->stream));
+        st = run_vote_device(h, bytes ? in_dev : nullptr, n_frames, roi_w, roi_h, window, votes,
+                             history_in ? in_dev + bytes : nullptr, history_out ? out_dev + bytes : nullptr,
+                             bytes ? out_dev : nullptr, h->stream);
+        if (st != DIPS_OK) return st;
+        if (bytes) DIPS_HIP(h, hipMemcpyAsync(mask_out, out_dev, bytes, hipMemcpyDeviceToHost, h->stream));
+        if (history_out)
+            DIPS_HIP(h, hipMemcpyAsync(history_out, out_dev + bytes, hist_bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

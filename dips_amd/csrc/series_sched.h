@@ -255,6 +255,39 @@ inline Geom mask_geometry(uint64_t frame_bytes, uint32_t n_frames, int unroll, u
     return q;
 }
 
+// The shortest part of the temporal vote at window k (mask_vote.hip): a part
+// reads the k - 1 frames before it to prime its counters, so parts of at
+// least 8 (k - 1) frames, and of at least cut_parts_to_fill's 16, keep those
+// reads at or below 1 / 8 of the frames read as input.
+inline uint32_t vote_min_part_frames(uint32_t window) { return std::max(16u, 8u * (window - 1u)); }
+
+// Geometry of the temporal vote on a mask (mask_vote.hip): a persistent grid
+// of occupancy x CUs waves over items (frame part, tile), a tile = 64 *
+// `words` mask words of the frame.  Parts by cut_parts_to_fill, as for the
+// mask itself (every word has one writer whatever the part count), then made
+// no shorter than vote_min_part_frames: every part but the last has at least
+// that many frames, so a part other than the first starts at or after frame
+// k - 1 and primes from input frames alone.  `frame_words` > 0, `window` >= 1.
+// Refused: no frames, 2^31 frames or more.
+inline Geom vote_geometry(uint64_t frame_words, uint32_t n_frames, uint32_t window, int words, uint64_t resident) {
+    Geom q;
+    const uint64_t wpt = 64u * (uint64_t)words;  // words per tile
+    const uint64_t n_tiles = (frame_words + wpt - 1) / wpt;
+    if (n_frames == 0 || n_frames >= (1u << 31) || resident == 0 || n_tiles == 0 || n_tiles >= (1ull << 31)) return q;
+    cut_parts_to_fill(q, n_tiles, n_frames, resident);
+    const uint32_t lmin = vote_min_part_frames(window);
+    if (q.part_frames < lmin) {
+        const uint32_t parts = std::max(1u, n_frames / lmin);
+        q.part_frames = (uint32_t)(((uint64_t)n_frames + parts - 1) / parts);
+        q.parts = (uint32_t)(((uint64_t)n_frames + q.part_frames - 1) / q.part_frames);
+        q.n_waves = std::min((uint64_t)q.parts * n_tiles, resident);
+    }
+    q.n_tiles = n_tiles;
+    q.blocks = (q.n_waves + 3) / 4;
+    q.ok = q.blocks < (1ull << 31);
+    return q;
+}
+
 // Geometry of the fast change-times kernel: pix_geometry's without a cap on
 // the frames of a part (the state is u32 indices and run lengths, nothing
 // overflows), and with the parts limited to what keeps their summaries (20

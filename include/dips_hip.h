@@ -657,6 +657,59 @@ dips_status dips_mask_morph(dips_handle *h, const uint8_t *mask_in, uint32_t n_f
                             uint32_t op, uint32_t shape, uint32_t rx, uint32_t ry,
                             uint8_t *mask_out);
 
+/* The temporal m-of-k vote on a change mask: the cleanup in time, where
+ * dips_mask_morph cleans in space (difference -> threshold -> vote ->
+ * morphology -> components).  The reference has no counterpart.  It reads a
+ * mask and writes a mask, so it serves every pixel format and every mask
+ * source, and the answer is exact.
+ * Input and output: both in exactly dips_diff_change_mask's layout.  With
+ * k = window, m = votes and X_t the input frame t, 0 <= t < n_frames:
+ *   out(t, j, i) = 1  iff  #{s: t - k + 1 <= s <= t, X_s(j, i) = 1} >= m.
+ * The vote is causal: output frame t belongs to input frame t and looks at
+ * it and the k - 1 frames before it.  The frames before the clip, X_{-(k-1)}
+ * .. X_{-1}, are the k - 1 frames of history_in, oldest first, in the same
+ * layout; history_in = NULL means that every frame before the clip is clear
+ * (with m = k the first k - 1 output frames are then all clear).
+ *   m = 1            temporal dilation (OR of the window): bridges dropouts
+ *   m = k            temporal erosion (AND); k = 2 on a 'per-frame' mask is
+ *                    the three-frame difference D_{t-1} AND D_t
+ *   m = k / 2 + 1    temporal median: removes flicker and fills dropouts
+ *                    shorter than k / 2 without touching shape
+ * The pad bits of mask_in and history_in are ignored, whatever they hold;
+ * those of mask_out and history_out are written as 0, and every byte of both
+ * outputs is written.
+ * history_out may be NULL.  When given it receives the last k - 1 frames of
+ * the sequence history ++ input: for n_frames >= k - 1 the last k - 1 input
+ * frames, otherwise the newest k - 1 - n_frames history frames (clear ones
+ * for NULL history) followed by the n_frames input frames.  It is written
+ * also when n_frames == 0 (the history with its pad bits zeroed, or all
+ * clear).  So a clip fed call by call, one call's history_out as the next
+ * call's history_in, gives byte for byte the output and the history of one
+ * call over the whole clip, for any chunking, one frame per call included.
+ * window = 1: votes must be 1, the call copies the mask with the pad bits
+ * zeroed, both history pointers are ignored and history_out is not written.
+ * window <= DIPS_VOTE_MAX_WINDOW = 31: the count of a pixel fits 5 bits.
+ * One launch per call and one more for history_out, no scratch;
+ * the time does not depend on the bits.
+ * DIPS_FLAG_DEVICE_PTRS: all pointers are device pointers, 4-byte aligned,
+ * the call asynchronous on the handle's stream; else host pointers of any
+ * alignment, staged through HBM, synchronous.  DIPS_FLAG_TIME_KERNEL: one
+ * entry for all launches of the call.  n_frames == 0: DIPS_OK, mask_out
+ * untouched, history_out written as above.  DIPS_ERR_INVALID, the outputs
+ * untouched: a null mask_in or mask_out with n_frames > 0, window of 0 or
+ * above DIPS_VOTE_MAX_WINDOW, votes of 0 or above window, roi_w or roi_h of
+ * 0, a region of 2^30 pixels or more, n_frames of 2^31 or more, a
+ * misaligned device pointer, and any
+ * overlap between the byte range of an output (mask_out: n_frames frames,
+ * history_out: window - 1 frames) and that of an input or of the other
+ * output (in place is refused, not silently wrong). */
+#define DIPS_VOTE_MAX_WINDOW 31u
+dips_status dips_mask_vote(dips_handle *h, const uint8_t *mask_in, uint32_t n_frames,
+                           uint32_t roi_w, uint32_t roi_h,
+                           uint32_t window, uint32_t votes,
+                           const uint8_t *history_in, uint8_t *history_out,
+                           uint8_t *mask_out);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,

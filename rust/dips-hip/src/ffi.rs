@@ -54,6 +54,7 @@ pub const DIPS_MORPH_CLOSE: u32 = 3;
 pub const DIPS_MORPH_BOX: u32 = 0;
 pub const DIPS_MORPH_DIAMOND: u32 = 1;
 pub const DIPS_MORPH_MAX_RADIUS: u32 = 15;
+pub const DIPS_VOTE_MAX_WINDOW: u32 = 31;
 pub const DIPS_BG_SELECTIVE: u32 = 1;
 pub const DIPS_BG_MAX_RATE_SHIFT: u32 = 8;
 pub const DIPS_SD_MAX_AMP: u32 = 15;
@@ -215,6 +216,8 @@ extern "C" {
                             links: *mut u32) -> DipsStatus;
     pub fn dips_mask_morph(h: *mut DipsHandle, mask_in: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, op: u32,
                            shape: u32, rx: u32, ry: u32, mask_out: *mut u8) -> DipsStatus;
+    pub fn dips_mask_vote(h: *mut DipsHandle, mask_in: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, window: u32,
+                          votes: u32, history_in: *const u8, history_out: *mut u8, mask_out: *mut u8) -> DipsStatus;
     pub fn dips_synth_frames(h: *mut DipsHandle, width: u32, height: u32, seed: u64, t0: u64, n_frames: u32,
                              dst: *mut u8) -> DipsStatus;
     pub fn dips_kernel_time(h: *mut DipsHandle, total_ms: *mut f64, launches: *mut u64) -> DipsStatus;
