@@ -206,6 +206,8 @@ def load() -> ctypes.CDLL:
             "dips_mask_tracks": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, _vp, _vp, _vp, _vp], st),
             "dips_mask_morph": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p], st),
             "dips_mask_vote": ([_vp, _u8p, u32, u32, u32, u32, u32, _u8p, _u8p, _u8p], st),
+            "dips_mask_counts": ([_vp, _u8p, u32, u32, u32, u32, u32, _vp], st),
+            "dips_mask_pixel_times": ([_vp, _u8p, u32, u32, u32, u32, u32, _vp, _vp], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),
             "dips_diff_series_streamed": ([_vp, u32, u32, _u8p, u32, _u8p, _vp, u32], st),
             "dips_synth_frames": ([_vp, u32, u32, u64, u64, u32, _u8p], st),

@@ -783,6 +783,63 @@ def _vote_option(vote) -> Tuple[int, int]:
     return _vote_args(vote)
 
 
+def _mask_host_args(mask) -> Tuple[np.ndarray, int, int, int]:
+    """(bits, region width, region height, n) of a host ChangeMask, checked
+    as the mask statistics take it."""
+    if not isinstance(mask, ChangeMask):
+        raise ValueError("mask must be a ChangeMask")
+    bits = np.ascontiguousarray(mask.bits, dtype=np.uint8)
+    rw = int(mask.width)
+    if bits.ndim != 3 or rw <= 0 or bits.shape[1] == 0 or bits.shape[2] != 4 * ((rw + 31) // 32):
+        raise ValueError("mask.bits must be [n, h, 4 * ceil(width / 32)] bytes, h and width not 0")
+    n, rh = int(bits.shape[0]), int(bits.shape[1])
+    if rw * rh >= 1 << 30:
+        raise ValueError("the region must stay below 2^30 pixels")
+    return bits, rw, rh, n
+
+
+def _mask_device_args(mask, width) -> Tuple[int, int, int]:
+    """(region width, region height, n) of a device mask tensor, checked."""
+    import torch
+    rw = int(width)
+    if mask.dim() != 3 or rw <= 0 or mask.shape[2] != 4 * ((rw + 31) // 32) or mask.dtype != torch.uint8:
+        raise ValueError("mask must be a uint8 tensor of shape [N, h, 4 * ceil(width / 32)]")
+    n, rh = int(mask.shape[0]), int(mask.shape[1])
+    if rh == 0:
+        raise ValueError("the mask's height must not be 0")
+    if rw * rh >= 1 << 30:
+        raise ValueError("the region must stay below 2^30 pixels")
+    return rw, rh, n
+
+
+def _mask_device_outputs(mask, outs) -> None:
+    """The device tensors of a mask statistic: contiguous HIP tensors, 4-byte
+    aligned, no output sharing a byte with the mask or another output."""
+    tensors = [mask] + list(outs)
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("device path needs contiguous HIP tensors")
+        if t.numel() and (t.data_ptr() & 3) != 0:
+            raise ValueError("the tensors must be 4-byte aligned")
+    spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in tensors if t.numel()]
+    for i, (a0, a1) in enumerate(spans):
+        for b0, b1 in spans[i + 1:]:
+            if a0 < b1 and b0 < a1:
+                raise ValueError("an output must not overlap the mask or the other output")
+
+
+def _mask_grid_args(rows, cols, rw: int, rh: int, n: int) -> Tuple[int, int]:
+    """(rows, cols) of dips_mask_counts over a region rw x rh, checked."""
+    rows, cols = int(rows), int(cols)
+    if rows < 1 or cols < 1:
+        raise ValueError("rows and cols must be at least 1")
+    if rows > rh or cols > rw:
+        raise ValueError("more rows or cols than the region has pixels (a cell would be empty)")
+    if n * rows * cols >= 1 << 30:
+        raise ValueError("n_frames * rows * cols must stay below 2^30")
+    return rows, cols
+
+
 def _roi_arg(roi):
     """roi (x, y, w, h) as the uint32[4] the C ABI takes, or None."""
     if roi is None:
@@ -1487,6 +1544,125 @@ class DiffSeriesOperator:
                 history.data_ptr() if history is not None else None,
                 history_out.data_ptr() if history_out is not None else None,
                 out.data_ptr() if n else None))
+
+    # -- the statistics of a change mask (dips_mask_counts, dips_mask_pixel_times)
+    def mask_counts(self, mask: ChangeMask, rows: int = 1, cols: int = 1) -> np.ndarray:
+        """uint32 [n, rows, cols]: the set bits of every frame of `mask` in
+        every cell of a rows x cols grid over its region, cut as grid_cell
+        cuts it (rows = cols = 1: the count series of the mask).  A mask that
+        lives on the device goes through run_mask_counts_device."""
+        bits, rw, rh, n = _mask_host_args(mask)
+        rows, cols = _mask_grid_args(rows, cols, rw, rh, n)
+        out = np.zeros((n, rows, cols), dtype=np.uint32)
+        self._host.check(self._host._lib.dips_mask_counts(
+            self._host.ptr, bits.ctypes.data if n else None, n, rw, rh, rows, cols, out.ctypes.data if n else None))
+        return out
+
+    def run_mask_counts_device(self, mask, width: int, counts_out, rows: int = 1, cols: int = 1, stream=None) -> None:
+        """Asynchronous: mask a uint8 device tensor [N, h, row_bytes] as
+        run_change_mask_device writes it for a region `width` pixels wide,
+        counts_out a 4-byte device tensor [N, rows, cols]; both 4-byte
+        aligned, not overlapping.  Every entry of counts_out is written."""
+        rw, rh, n = _mask_device_args(mask, width)
+        rows, cols = _mask_grid_args(rows, cols, rw, rh, n)
+        if tuple(counts_out.shape) != (n, rows, cols) or counts_out.element_size() != 4:
+            raise ValueError("counts_out must be a 4-byte tensor of shape [N, rows, cols]")
+        _mask_device_outputs(mask, [counts_out])
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_counts(
+                self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, rows, cols,
+                counts_out.data_ptr() if n else None))
+
+    def _mask_times_host(self, mask_args, t0: int, times: Optional[np.ndarray], sums: Optional[np.ndarray],
+                         accumulate: bool) -> None:
+        bits, rw, rh, n = mask_args
+        for out, planes in ((times, (4, rh, rw)), (sums, (rh, rw))):
+            if out is not None and out.shape != planes:
+                raise ValueError("into must hold the result of the same region")
+        if int(t0) < 0 or int(t0) > 0xFFFFFFFF:
+            raise ValueError("t0 must be a non-negative 32-bit integer")
+        self._host.check(self._host._lib.dips_mask_pixel_times(
+            self._host.ptr, bits.ctypes.data if n else None, n, rw, rh, int(t0), 1 if accumulate else 0,
+            times.ctypes.data if times is not None else None, sums.ctypes.data if sums is not None else None))
+
+    def mask_times(self, mask: ChangeMask, t0: int = 0, into: Optional[PixelTimes] = None) -> PixelTimes:
+        """The change times of `mask` per pixel, as pixel_times gives them
+        for the raw change mask: first, last, run_max, run_cur; frame t of
+        the mask has the global index t0 + t.  `into`: a PixelTimes of the
+        same region to fold onto (a clip in chunks: t0 = the frames folded so
+        far); any chunking gives what one call gives."""
+        if into is not None and not isinstance(into, PixelTimes):
+            raise ValueError("into must be a PixelTimes")
+        args = _mask_host_args(mask)
+        if into is not None:
+            out = np.ascontiguousarray(into.as_array(), dtype=np.uint32)
+        else:
+            out = np.zeros((4, args[2], args[1]), dtype=np.uint32)
+        self._mask_times_host(args, t0, out, None, into is not None)
+        return PixelTimes.from_array(out)
+
+    def mask_sums(self, mask: ChangeMask, into: Optional[np.ndarray] = None) -> np.ndarray:
+        """uint32 [h, w]: in how many frames of `mask` each pixel is set
+        (pixel_sums' count for the raw change mask), modulo 2^32.  `into`:
+        such an array to add onto (it is not modified)."""
+        args = _mask_host_args(mask)
+        if into is not None:
+            out = np.array(into, dtype=np.uint32, order="C")
+        else:
+            out = np.zeros((args[2], args[1]), dtype=np.uint32)
+        self._mask_times_host(args, 0, None, out, into is not None)
+        return out
+
+    def run_mask_times_device(self, mask, width: int, times_out=None, sums_out=None, t0: int = 0,
+                              accumulate: bool = False, stream=None) -> None:
+        """Asynchronous: mask a uint8 device tensor [N, h, row_bytes] as
+        run_change_mask_device writes it for a region `width` pixels wide,
+        times_out a 4-byte device tensor [4, h, w], sums_out one of [h, w]
+        (either may be None, not both), overwritten or (accumulate) folded
+        onto; all 4-byte aligned, no output overlapping the mask or the
+        other output.  One read of the mask serves both outputs."""
+        rw, rh, n = _mask_device_args(mask, width)
+        if times_out is None and sums_out is None:
+            raise ValueError("times_out and sums_out must not both be None")
+        if times_out is not None and (tuple(times_out.shape) != (4, rh, rw) or times_out.element_size() != 4):
+            raise ValueError("times_out must be a 4-byte tensor of shape [4, h, w] of the region")
+        if sums_out is not None and (tuple(sums_out.shape) != (rh, rw) or sums_out.element_size() != 4):
+            raise ValueError("sums_out must be a 4-byte tensor of shape [h, w] of the region")
+        if int(t0) < 0 or int(t0) > 0xFFFFFFFF:
+            raise ValueError("t0 must be a non-negative 32-bit integer")
+        if times_out is not None and int(t0) + n > 0xFFFFFFFF:
+            raise ValueError("t0 + n_frames must stay below 2^32")
+        _mask_device_outputs(mask, [t for t in (times_out, sums_out) if t is not None])
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_pixel_times(
+                self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, int(t0), 1 if accumulate else 0,
+                times_out.data_ptr() if times_out is not None else None,
+                sums_out.data_ptr() if sums_out is not None else None))
+
+    def change_activity(self, frames, roi=None, ref=None, rows: int = 1, cols: int = 1, morph=None, background=None,
+                        sigma_delta=None, vote=None) -> Tuple[np.ndarray, PixelTimes, np.ndarray]:
+        """(counts, times, sums) of the cleaned change mask, with the mask
+        kept on the device: change_boxes' mask (its roi, ref, background,
+        sigma_delta, vote and morph arguments), then mask_counts on a rows x
+        cols grid, mask_times from t0 = 0 and mask_sums."""
+        import torch
+        _mask_grid_args(rows, cols, 0xFFFFFFFF, 0xFFFFFFFF, 0)  # before any device work; the region is checked below
+        mask, rw, rh, n = self._change_mask_on_device(frames, roi, ref, morph, background, lambda n_: None,
+                                                      sigma_delta, vote)
+        rows, cols = _mask_grid_args(rows, cols, rw, rh, n)
+        dev = mask.device
+        counts = torch.empty((n, rows, cols), dtype=torch.int32, device=dev)
+        times = torch.empty((4, rh, rw), dtype=torch.int32, device=dev)
+        sums = torch.empty((rh, rw), dtype=torch.int32, device=dev)
+        self.run_mask_counts_device(mask, rw, counts, rows, cols)
+        self.run_mask_times_device(mask, rw, times, sums)
+
+        def to_u32(t):
+            return t.cpu().numpy().view(np.uint32)  # the copy waits for the stream
+
+        return to_u32(counts), PixelTimes.from_array(to_u32(times)), to_u32(sums)
 
     def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args, sigma_delta=None, vote=None):
         """(mask, region width, region height, n): the change mask of

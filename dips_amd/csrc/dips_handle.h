@@ -7,7 +7,8 @@
 //   series_abi.hip  the north-star difference series and its measurement legs
 //   region_abi.hip  the regional products: grid, pixel sums, change mask,
 //                   pixel times, background and Sigma-Delta models
-//   mask_abi.hip    the mask products: components, tracks, morphology, vote
+//   mask_abi.hip    the mask products: components, tracks, morphology, vote,
+//                   statistics
 //   shard_abi.hip   the frame-range sharding of the series
 // (series_host.h: what the series, region and mask units share; series_sched.h:
 // their schedules as functions of plain numbers.)
@@ -48,6 +49,7 @@ struct dips_handle {
     dips_host::DevBuf partials, stage_frames, stage_ref, stage_series, stage_map;
     dips_host::DevBuf probe_out;  // sink of the read-ceiling kernels
     dips_host::DevBuf times_parts;  // per-part summaries of dips_diff_pixel_times (series_times.hip)
+                                    // and of dips_mask_pixel_times (mask_stats.hip)
     dips_host::DevBuf cc_scratch;   // union-find and statistics of dips_mask_components (mask_components.hip),
                                     // the overlap tables and the carry of dips_mask_tracks (mask_tracks.hip)
     std::map<const void*, int> occupancy;

@@ -77,6 +77,16 @@
 //            the final state, the planes M and V of roi_h x roi_w
 //            little-endian u16, and the stdout line ends with
 //            sigma_delta=N,VMIN,VMAX
+//            [--mask-counts FILE [--mask-grid RxC]] [--mask-times FILE]
+//            [--mask-sums FILE] -> the statistics of the final mask (behind
+//            --background / --sigma-delta, --vote and --morph; --roi as for
+//            --mask) with dips_mask_counts and dips_mask_pixel_times, with
+//            --mask, --boxes or --tracks or on their own (the stdout line then
+//            begins with "mask-stats" and no mask is written): the counts as
+//            the CSV t,row,col,count over an R x C grid of the region (default
+//            1x1: the set bits per frame), the times as --pixel-times writes
+//            them, the sums as one plane of roi_h x roi_w little-endian u32;
+//            the stdout line ends with mask_stats=<what was written>
 //   dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode ...]
 //            [--tau T] [--transport loopback|rccl]
 //                                         -> the same CSV, computed by N
@@ -148,6 +158,9 @@ int usage() {
                  "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask, --boxes or --tracks)\n"
                  "                [--background K[,selective] [--background-out FILE]] (with --mask, --boxes or --tracks)\n"
                  "                [--sigma-delta N[,VMIN[,VMAX]] [--sigma-delta-out FILE]] (likewise; not with --background)\n"
+                 "                [--mask-counts FILE [--mask-grid RxC]] [--mask-times FILE] [--mask-sums FILE]\n"
+                 "                (of the final mask; alone or with --mask, --boxes or --tracks; take --roi, --vote,\n"
+                 "                --morph, --background and --sigma-delta as --mask does)\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -327,6 +340,94 @@ int apply_morph(dips_handle* hd, std::vector<uint8_t>& mask, uint32_t n, uint32_
         mask.swap(other);
     }
     return DIPS_OK;
+}
+
+// --mask-counts [--mask-grid], --mask-times, --mask-sums: the statistics of
+// the final mask (dips_mask_counts, dips_mask_pixel_times).
+struct StatsOpt {
+    const char* counts_path = nullptr;
+    const char* times_path = nullptr;
+    const char* sums_path = nullptr;
+    uint32_t rows = 1, cols = 1;
+    bool has_grid = false;
+    bool on() const { return counts_path || times_path || sums_path; }
+};
+
+struct StatsOut {
+    std::vector<uint32_t> counts, times, sums;
+};
+
+// The statistics asked for of the host mask of n frames of rw x rh pixels
+// into `out`; the status of the first call that fails, named in *what.
+int mask_stats(dips_handle* hd, const std::vector<uint8_t>& mask, uint32_t n, uint32_t rw, uint32_t rh,
+               const StatsOpt& so, StatsOut* out, const char** what) {
+    const size_t npx = (size_t)rw * rh;
+    if (so.counts_path) {
+        // a grid the library will refuse gets one entry: nothing is written to it
+        const bool sane = so.rows <= rh && so.cols <= rw && (uint64_t)n * so.rows * so.cols < (1ull << 30);
+        out->counts.assign(sane ? (size_t)n * so.rows * so.cols : 1u, 0u);
+        *what = "dips_mask_counts";
+        const int st = dips_mask_counts(hd, mask.data(), n, rw, rh, so.rows, so.cols, out->counts.data());
+        if (st != DIPS_OK) return st;
+        if (n == 0) out->counts.clear();
+    }
+    if (so.times_path || so.sums_path) {
+        if (so.times_path) out->times.assign(DIPS_TIMES_PLANES * npx, 0u);
+        if (so.sums_path) out->sums.assign(npx, 0u);
+        *what = "dips_mask_pixel_times";
+        return dips_mask_pixel_times(hd, n ? mask.data() : nullptr, n, rw, rh, 0u, 0u,
+                                     so.times_path ? out->times.data() : nullptr,
+                                     so.sums_path ? out->sums.data() : nullptr);
+    }
+    return DIPS_OK;
+}
+
+bool write_u32_file(const char* path, const std::vector<uint32_t>& v) {
+    std::FILE* f = std::fopen(path, "wb");
+    if (!f || std::fwrite(v.data(), sizeof(uint32_t), v.size(), f) != v.size() || std::fclose(f) != 0) {
+        std::fprintf(stderr, "dips_raw: cannot write %s\n", path);
+        return false;
+    }
+    return true;
+}
+
+// The files of the statistics: the counts as the CSV t,row,col,count, the
+// times as --pixel-times writes them, the sums as one plane of roi_h x roi_w
+// little-endian u32 (0: written or not asked for).
+int write_mask_stats(const StatsOpt& so, const StatsOut& out) {
+    if (so.counts_path) {
+        std::FILE* f = std::fopen(so.counts_path, "w");
+        if (!f) {
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", so.counts_path);
+            return 1;
+        }
+        std::fprintf(f, "t,row,col,count\n");
+        const size_t cells = (size_t)so.rows * so.cols;
+        for (size_t i = 0; i < out.counts.size(); ++i)
+            std::fprintf(f, "%zu,%zu,%zu,%u\n", i / cells, (i % cells) / so.cols, i % so.cols, out.counts[i]);
+        if (std::ferror(f) != 0 || std::fclose(f) != 0) {
+            std::fprintf(stderr, "dips_raw: cannot write %s\n", so.counts_path);
+            return 1;
+        }
+    }
+    if (so.times_path && !write_u32_file(so.times_path, out.times)) return 1;
+    if (so.sums_path && !write_u32_file(so.sums_path, out.sums)) return 1;
+    return 0;
+}
+
+void print_mask_stats(const StatsOpt& so) {
+    if (!so.on()) return;
+    std::printf(" mask_stats=");
+    const char* sep = "";
+    if (so.counts_path) {
+        std::printf("counts:%ux%u", so.rows, so.cols);
+        sep = ",";
+    }
+    if (so.times_path) {
+        std::printf("%stimes", sep);
+        sep = ",";
+    }
+    if (so.sums_path) std::printf("%ssums", sep);
 }
 
 // "x,y,w,h" -> roi[4] (decimal, zero allowed; the library checks the extent)
@@ -609,6 +710,7 @@ int run_series(int argc, char** argv) {
     VoteOpt vote;
     BackgroundOpt bg;
     SigmaDeltaOpt sd;
+    StatsOpt stats;
     if (!parse_u32(argv[3], &w) || !parse_u32(argv[4], &h)) return usage();
     dips_params p;
     dips_params_default(&p);
@@ -659,6 +761,15 @@ int run_series(int argc, char** argv) {
             if (!parse_sigma_delta(argv[++i], &sd)) return usage();
         } else if (a == "--sigma-delta-out" && has) {
             sd.out_path = argv[++i];
+        } else if (a == "--mask-counts" && has) {
+            stats.counts_path = argv[++i];
+        } else if (a == "--mask-grid" && has) {
+            if (!parse_grid(argv[++i], &stats.rows, &stats.cols)) return usage();
+            stats.has_grid = true;
+        } else if (a == "--mask-times" && has) {
+            stats.times_path = argv[++i];
+        } else if (a == "--mask-sums" && has) {
+            stats.sums_path = argv[++i];
         } else if (a == "--roi" && has) {
             if (!parse_roi(argv[++i], roi)) return usage();
             has_roi = true;
@@ -666,16 +777,20 @@ int run_series(int argc, char** argv) {
             return usage();
         }
     }
-    // --morph belongs to --mask, --boxes or --tracks
-    if (!morph.empty() && !mask_path && !boxes_path && !tracks_path) return usage();
+    // --mask-grid belongs to --mask-counts; the statistics are the mask's, not --grid's, --pixel-sums' or --pixel-times'
+    if ((stats.has_grid && !stats.counts_path) || (stats.on() && (rows != 0 || pix_path || times_path))) return usage();
+    // what takes a mask: --mask, --boxes, --tracks or a statistic of the mask
+    const bool masked = mask_path || boxes_path || tracks_path || stats.on();
+    // --morph belongs to those
+    if (!morph.empty() && !masked) return usage();
     // so does --vote
-    if (vote.window != 0u && !mask_path && !boxes_path && !tracks_path) return usage();
-    // --background belongs to --mask, --boxes or --tracks, --background-out to --background
-    if ((bg.on && !mask_path && !boxes_path && !tracks_path) || (bg.out_path && !bg.on)) return usage();
+    if (vote.window != 0u && !masked) return usage();
+    // --background too, --background-out to --background
+    if ((bg.on && !masked) || (bg.out_path && !bg.on)) return usage();
     // so does --sigma-delta, --sigma-delta-out to --sigma-delta; the two models exclude each other
-    if ((sd.on && !mask_path && !boxes_path && !tracks_path) || (sd.out_path && !sd.on) || (sd.on && bg.on)) return usage();
-    // --roi belongs to --grid, --pixel-sums, --mask, --pixel-times, --boxes or --tracks
-    if (has_roi && rows == 0 && !pix_path && !mask_path && !times_path && !boxes_path && !tracks_path) return usage();
+    if ((sd.on && !masked) || (sd.out_path && !sd.on) || (sd.on && bg.on)) return usage();
+    // --roi belongs to --grid, --pixel-sums, --pixel-times or what takes a mask
+    if (has_roi && rows == 0 && !pix_path && !times_path && !masked) return usage();
     if ((rows != 0) + (pix_path != nullptr) + (mask_path != nullptr) + (times_path != nullptr) +
             (boxes_path != nullptr) + (tracks_path != nullptr) > 1)
         return usage();
@@ -745,7 +860,7 @@ int run_series(int argc, char** argv) {
                     has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, tot[0], tot[1], tot[2], tot[3]);
         return 0;
     }
-    if (mask_path) {
+    if (mask_path || (stats.on() && !boxes_path && !tracks_path)) {  // the statistics alone: the mask is not written
         const uint32_t rw = has_roi ? roi[2] : w, rh = has_roi ? roi[3] : h;
         // a region the library will refuse gets one byte: nothing is written to it
         uint32_t rect[4];
@@ -764,6 +879,8 @@ int run_series(int argc, char** argv) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
         }
+        StatsOut stats_out;
+        if (st == DIPS_OK) st = mask_stats(hd, mask, n, rw, rh, stats, &stats_out, &what);
         if (st != DIPS_OK) {
             const int rc = lib_error(hd, what, st);
             dips_destroy(hd);
@@ -771,20 +888,23 @@ int run_series(int argc, char** argv) {
         }
         dips_destroy(hd);
         if (n == 0) mask.clear();
-        if (write_background(bg, sd, state) != 0) return 1;
-        // frames x roi_h x row_bytes, bit i of a row = bit (i & 7) of byte (i >> 3)
-        std::FILE* f = std::fopen(mask_path, "wb");
-        if (!f || std::fwrite(mask.data(), 1, mask.size(), f) != mask.size() || std::fclose(f) != 0) {
-            std::fprintf(stderr, "dips_raw: cannot write %s\n", mask_path);
-            return 1;
+        if (write_background(bg, sd, state) != 0 || write_mask_stats(stats, stats_out) != 0) return 1;
+        if (mask_path) {
+            // frames x roi_h x row_bytes, bit i of a row = bit (i & 7) of byte (i >> 3)
+            std::FILE* f = std::fopen(mask_path, "wb");
+            if (!f || std::fwrite(mask.data(), 1, mask.size(), f) != mask.size() || std::fclose(f) != 0) {
+                std::fprintf(stderr, "dips_raw: cannot write %s\n", mask_path);
+                return 1;
+            }
         }
         unsigned long long set = 0;
         for (const uint8_t b : mask) set += (unsigned long long)__builtin_popcount(b);
-        std::printf("mask roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu", has_roi ? roi[0] : 0u,
-                    has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
+        std::printf("%s roi=%u,%u,%u,%u frames=%u row_bytes=%u set=%llu", mask_path ? "mask" : "mask-stats",
+                    has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
         if (vote.window != 0u) std::printf(" vote=%u,%u", vote.window, vote.votes);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
         print_background(bg, sd);
+        print_mask_stats(stats);
         std::printf("\n");
         return 0;
     }
@@ -823,13 +943,15 @@ int run_series(int argc, char** argv) {
             st = dips_mask_components(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, counts.data(),
                                       max_boxes ? recs.data() : nullptr, nullptr);
         }
+        StatsOut stats_out;
+        if (st == DIPS_OK) st = mask_stats(hd, mask, n, rw, rh, stats, &stats_out, &what);
         if (st != DIPS_OK) {
             const int rc = lib_error(hd, what, st);
             dips_destroy(hd);
             return rc;
         }
         dips_destroy(hd);
-        if (write_background(bg, sd, state) != 0) return 1;
+        if (write_background(bg, sd, state) != 0 || write_mask_stats(stats, stats_out) != 0) return 1;
         std::FILE* f = std::fopen(out_path, "w");
         if (!f) {
             std::fprintf(stderr, "dips_raw: cannot write %s\n", out_path);
@@ -863,6 +985,7 @@ int run_series(int argc, char** argv) {
         if (vote.window != 0u) std::printf(" vote=%u,%u", vote.window, vote.votes);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
         print_background(bg, sd);
+        print_mask_stats(stats);
         std::printf("\n");
         return 0;
     }

@@ -1,6 +1,7 @@
 // mask_abi.hip -- host side of include/dips_hip.h, part 5: the products of a
 // packed change mask -- its connected components, the components linked
-// across frames (tracks), the binary morphology and the temporal vote.  What
+// across frames (tracks), the binary morphology, the temporal vote and the
+// statistics (grid counts, change times and per-pixel sums).  What
 // they share with the series and the regional products is in series_host.h.
 // Every extern "C" body runs inside dips_abi::guard (abi_guard.h).
 #include <hip/hip_runtime.h>
@@ -291,9 +292,192 @@ dips_status run_vote_device(dips_handle* h, const uint8_t* mask_in, uint32_t n_f
     return span.end(s);
 }
 
+// ---------------------------------------------------------------------------
+// The statistics of a mask (dips_mask_counts, dips_mask_pixel_times; kernels
+// in mask_stats.hip)
+// ---------------------------------------------------------------------------
+
+// the parts' summaries of dips_mask_pixel_times stay within this (the handle's times_parts)
+constexpr uint64_t kMaskTimesPartsBytes = 1ull << 30;
+
+// whether two byte ranges share a byte
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && na != 0 && nb != 0 && pa < pb + nb && pb < pa + na;
+}
+
+// The grid counts of a device mask, asynchronously on `s`: the clear of
+// counts where several blocks add to a cell, and one launch.
+dips_status run_counts_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                              uint32_t rows, uint32_t cols, uint32_t* counts, hipStream_t s) {
+    const uint64_t resident = (uint64_t)std::max(0, occupancy_blocks(h, dips::mask_counts_kernel_ptr())) * h->cu_count;
+    const dips_sched::CountsGeom q = dips_sched::mask_counts_geometry(
+        w, hgt, rows, cols, n_frames, dips::kCountsChunkCells, dips::kCountsMinBandWords, resident);
+    if (!q.ok) return fail(h, DIPS_ERR_HIP, "mask_counts: no schedule for this mask");
+    dips::MaskCountsArgs a{};
+    a.mask = reinterpret_cast<const uint32_t*>(mask);
+    a.counts = counts;
+    a.items = q.items;
+    a.w = w;
+    a.h = hgt;
+    a.wpr = (uint32_t)mask_words_per_row(w);
+    a.n_frames = n_frames;
+    a.rows = rows;
+    a.cols = cols;
+    a.col_chunks = q.col_chunks;
+    a.bands = q.bands;
+    a.band_rows = q.band_rows;
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    if (q.bands > 1u) DIPS_HIP(h, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)n_frames * rows * cols, s));
+    DIPS_HIP(h, dips::launch_mask_counts(a, (uint32_t)q.blocks, s));
+    return span.end(s);
+}
+
+// The change times and / or sums of a device mask, asynchronously on `s`:
+// one launch, and the fold of the parts where the frames are cut; with no
+// frames the initial state.  times or sums may be NULL, not both.
+dips_status run_mask_times_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                                  uint32_t t0, bool accumulate, uint32_t* times, uint32_t* sums, hipStream_t s) {
+    const size_t npx = (size_t)w * hgt;
+    if (n_frames == 0) {
+        if (accumulate) return DIPS_OK;
+        KernelSpan span(h);
+        DIPS_TRY(span.begin(s));
+        if (times) {
+            DIPS_HIP(h, hipMemsetAsync(times, 0xFF, sizeof(uint32_t) * 2u * npx, s));  // first, last = DIPS_TIME_NONE
+            DIPS_HIP(h, hipMemsetAsync(times + 2u * npx, 0, sizeof(uint32_t) * 2u * npx, s));
+        }
+        if (sums) DIPS_HIP(h, hipMemsetAsync(sums, 0, sizeof(uint32_t) * npx, s));
+        return span.end(s);
+    }
+    dips::MaskTimesArgs a{};
+    a.mask = mask;
+    a.times = times;
+    a.sums = sums;
+    a.w = w;
+    a.h = hgt;
+    a.row_bytes = (uint32_t)(4u * mask_words_per_row(w));
+    a.frame_bytes = a.row_bytes * hgt;
+    a.n_frames = n_frames;
+    a.t0 = t0;
+    a.accumulate = accumulate ? 1u : 0u;
+    const uint64_t summary = sizeof(uint32_t) * ((times ? 5u : 0u) + (sums ? 1u : 0u)) * (uint64_t)npx;
+    // the slots of the several-parts form: that is the form the parts would run
+    dips_sched::Geom q = dips_sched::mask_times_geometry(
+        (uint64_t)a.frame_bytes * (8 / dips::kMaskTimesPx), n_frames, summary, kMaskTimesPartsBytes,
+        resident_waves(h, dips::mask_times_kernel_ptr(times != nullptr, sums != nullptr, true)));
+    if (q.ok && q.parts == 1u)
+        q = dips_sched::mask_times_geometry(
+            (uint64_t)a.frame_bytes * (8 / dips::kMaskTimesPx), n_frames, summary, 0u,
+            resident_waves(h, dips::mask_times_kernel_ptr(times != nullptr, sums != nullptr, false)));
+    if (!q.ok) return fail(h, DIPS_ERR_HIP, "mask_pixel_times: no schedule for this mask");
+    a.part_frames = q.part_frames;
+    a.n_parts = q.parts;
+    a.n_tiles = (uint32_t)q.n_tiles;
+    a.n_waves = (uint32_t)q.n_waves;
+    // the scratch before the timed span (growing it synchronises)
+    if (q.parts > 1u) {
+        DIPS_HIP(h, h->times_parts.ensure((size_t)(summary * q.parts)));
+        a.parts = h->times_parts.as<uint32_t>();
+    }
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    DIPS_HIP(h, dips::launch_mask_times(a, (uint32_t)q.blocks, s));
+    if (q.parts > 1u) DIPS_HIP(h, dips::launch_mask_times_combine(a, s));
+    return span.end(s);
+}
+
 }  // namespace
 
 extern "C" {
+
+dips_status dips_mask_counts(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                             uint32_t rows, uint32_t cols, uint32_t* counts) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_counts: roi_w and roi_h must not be 0");
+        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_counts: the region must stay below 2^30 pixels");
+        if (rows == 0 || cols == 0) return fail(h, DIPS_ERR_INVALID, "mask_counts: rows and cols must be at least 1");
+        if (rows > roi_h || cols > roi_w)
+            return fail(h, DIPS_ERR_INVALID,
+                        "mask_counts: more rows or cols than the region has pixels (a cell would be empty)");
+        if ((uint64_t)n_frames * rows * cols >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_counts: n_frames * rows * cols must stay below 2^30");
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask || !counts) return fail(h, DIPS_ERR_INVALID, "mask_counts: null argument");
+        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const size_t counts_bytes = sizeof(uint32_t) * (size_t)n_frames * rows * cols;
+        if (ranges_overlap(counts, counts_bytes, mask, mask_bytes))
+            return fail(h, DIPS_ERR_INVALID, "mask_counts: counts must not overlap mask");
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_counts", {mask, counts}));
+            return run_counts_device(h, mask, n_frames, roi_w, roi_h, rows, cols, counts, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call)
+        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes));
+        DIPS_HIP(h, h->stage_series.ensure(counts_bytes));
+        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        st = run_counts_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, rows, cols,
+                               h->stage_series.as<uint32_t>(), h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(counts, h->stage_series.p, counts_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_pixel_times(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w,
+                                  uint32_t roi_h, uint32_t t0, uint32_t accumulate, uint32_t* times, uint32_t* sums) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (!times && !sums) return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: times and sums are both null");
+        if (!mask && n_frames > 0) return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: null argument");
+        if (roi_w == 0 || roi_h == 0)
+            return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: roi_w and roi_h must not be 0");
+        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: the region must stay below 2^30 pixels");
+        if (times && (uint64_t)t0 + n_frames > 0xFFFFFFFFull)
+            return fail(h, DIPS_ERR_INVALID,
+                        "mask_pixel_times: t0 + n_frames must stay below 2^32 (index 0xFFFFFFFF is DIPS_TIME_NONE)");
+        const size_t npx = (size_t)roi_w * roi_h;
+        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const size_t times_bytes = times ? sizeof(uint32_t) * DIPS_TIMES_PLANES * npx : 0u;
+        const size_t sums_bytes = sums ? sizeof(uint32_t) * npx : 0u;
+        if (ranges_overlap(times, times_bytes, mask, mask_bytes) || ranges_overlap(sums, sums_bytes, mask, mask_bytes) ||
+            ranges_overlap(times, times_bytes, sums, sums_bytes))
+            return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: an output must not overlap the mask or the other output");
+        if (n_frames == 0) mask = nullptr;
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_pixel_times", {mask, times, sums}));
+            return run_mask_times_device(h, mask, n_frames, roi_w, roi_h, t0, accumulate != 0u, times, sums, h->stream);
+        }
+        if (n_frames == 0 && accumulate != 0u) return DIPS_OK;
+        // host pointers: stage through HBM (synchronous call); the sums behind
+        // the times, the state uploaded first when accumulating
+        if (mask_bytes) DIPS_HIP(h, h->stage_frames.ensure(mask_bytes));
+        DIPS_HIP(h, h->stage_series.ensure(times_bytes + sums_bytes));
+        uint32_t* times_dev = times ? h->stage_series.as<uint32_t>() : nullptr;
+        uint32_t* sums_dev = sums ? h->stage_series.as<uint32_t>() + times_bytes / sizeof(uint32_t) : nullptr;
+        if (mask_bytes) DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        if (accumulate != 0u) {
+            if (times) DIPS_HIP(h, hipMemcpyAsync(times_dev, times, times_bytes, hipMemcpyHostToDevice, h->stream));
+            if (sums) DIPS_HIP(h, hipMemcpyAsync(sums_dev, sums, sums_bytes, hipMemcpyHostToDevice, h->stream));
+        }
+        st = run_mask_times_device(h, mask_bytes ? h->stage_frames.as<uint8_t>() : nullptr, n_frames, roi_w, roi_h, t0,
+                                   accumulate != 0u, times_dev, sums_dev, h->stream);
+        if (st != DIPS_OK) return st;
+        if (times) DIPS_HIP(h, hipMemcpyAsync(times, times_dev, times_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (sums) DIPS_HIP(h, hipMemcpyAsync(sums, sums_dev, sums_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
 
 dips_status dips_mask_components(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w,
                                  uint32_t roi_h, uint32_t connectivity, uint32_t min_area, uint32_t max_boxes,

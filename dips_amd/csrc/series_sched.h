@@ -288,6 +288,69 @@ inline Geom vote_geometry(uint64_t frame_words, uint32_t n_frames, uint32_t wind
     return q;
 }
 
+// Geometry of the change times and per-pixel sums of a mask (mask_stats.hip
+// mask_times_kernel): a persistent grid of occupancy x CUs waves over items
+// (frame part, tile), a tile = 64 lane slots of `frame_slots` (a slot is the
+// few pixels of one mask byte that a lane owns).  Parts by
+// cut_parts_unless_full, as for the change times of the frames: one part
+// unless the tiles leave wave slots empty, then parts of >= 16 frames, at most
+// what keeps the summaries (`summary_bytes` per part) within `parts_bytes`.
+// The parts [p L, min(n, (p + 1) L)) tile the frames and the combine folds
+// them in order, so the result does not depend on the cut.  Refused: no
+// frames, no slots, 2^31 tiles or more.
+inline Geom mask_times_geometry(uint64_t frame_slots, uint32_t n_frames, uint64_t summary_bytes, uint64_t parts_bytes,
+                                uint64_t resident) {
+    Geom q;
+    const uint64_t n_tiles = (frame_slots + 63u) / 64u;
+    if (n_frames == 0 || resident == 0 || n_tiles == 0 || n_tiles >= (1ull << 31) || summary_bytes == 0) return q;
+    const uint64_t max_parts = std::max<uint64_t>(1, parts_bytes / summary_bytes);
+    cut_parts_unless_full(q, n_tiles, n_frames, resident, max_parts, 0, 0);
+    q.n_tiles = n_tiles;
+    q.n_waves = std::min((uint64_t)q.parts * n_tiles, resident);
+    q.blocks = (q.n_waves + 3) / 4;
+    q.ok = q.blocks < (1ull << 31);
+    return q;
+}
+
+// Geometry of the grid counts of a mask (mask_stats.hip mask_counts_kernel).
+// An item is (frame, grid row, chunk of at most `chunk_cells` grid columns,
+// band of at most band_rows mask rows of that grid row): a block sums its
+// item per cell in registers and LDS and adds each cell once.  The bands cut
+// the tallest grid row, ceil(roi_h / rows) mask rows; a band that starts
+// below a shorter grid row's end is empty.  Enough bands to give every
+// resident block two items, none thinner than `min_band_words` mask words of
+// its chunk.  bands == 1: a cell has one writer and is stored; else the
+// blocks add with integer atomics onto cleared counts.  Refused: no frames,
+// an empty region or grid, a grid finer than the region.
+struct CountsGeom {
+    bool ok = false;
+    uint32_t col_chunks = 0;  // chunks of grid columns
+    uint32_t bands = 0;       // bands per grid row
+    uint32_t band_rows = 0;   // mask rows per band
+    uint64_t items = 0, blocks = 0;
+};
+
+inline CountsGeom mask_counts_geometry(uint32_t roi_w, uint32_t roi_h, uint32_t rows, uint32_t cols, uint32_t n_frames,
+                                       uint32_t chunk_cells, uint32_t min_band_words, uint64_t resident_blocks) {
+    CountsGeom q;
+    if (roi_w == 0 || roi_h == 0 || rows == 0 || cols == 0 || rows > roi_h || cols > roi_w || n_frames == 0 ||
+        chunk_cells == 0 || min_band_words == 0 || resident_blocks == 0)
+        return q;
+    q.col_chunks = (uint32_t)(((uint64_t)cols + chunk_cells - 1) / chunk_cells);
+    const uint64_t base = (uint64_t)n_frames * rows * q.col_chunks;
+    const uint64_t max_h = ((uint64_t)roi_h + rows - 1) / rows;
+    const uint64_t chunk_words = (mask_words_per_row(roi_w) + q.col_chunks - 1) / q.col_chunks;
+    const uint64_t min_rows = std::max<uint64_t>(1, ((uint64_t)min_band_words + chunk_words - 1) / chunk_words);
+    const uint64_t want = (2 * resident_blocks + base - 1) / base;
+    const uint64_t bands = std::max<uint64_t>(1, std::min(want, (max_h + min_rows - 1) / min_rows));
+    q.band_rows = (uint32_t)((max_h + bands - 1) / bands);
+    q.bands = (uint32_t)((max_h + q.band_rows - 1) / q.band_rows);
+    q.items = base * q.bands;
+    q.blocks = std::min(q.items, 2 * resident_blocks);
+    q.ok = q.blocks < (1ull << 31);
+    return q;
+}
+
 // Geometry of the fast change-times kernel: pix_geometry's without a cap on
 // the frames of a part (the state is u32 indices and run lengths, nothing
 // overflows), and with the parts limited to what keeps their summaries (20

@@ -710,6 +710,53 @@ dips_status dips_mask_vote(dips_handle *h, const uint8_t *mask_in, uint32_t n_fr
                            const uint8_t *history_in, uint8_t *history_out,
                            uint8_t *mask_out);
 
+/* The statistics of a change mask: what dips_diff_series_grid,
+ * dips_diff_pixel_sums and dips_diff_pixel_times give for the raw decision
+ * |dI| > tau, for any mask -- one taken against a background model, or
+ * cleaned by dips_mask_vote or dips_mask_morph.  The reference has no
+ * counterpart.  Both calls read a mask in exactly dips_diff_change_mask's
+ * layout for a region roi_w x roi_h, so they serve every pixel format and
+ * every mask source; the pad bits of the input are ignored, whatever they
+ * hold; the answers are exact.
+ *
+ * dips_mask_counts: counts[(t*rows + r)*cols + c] is the number of set bits
+ * of frame t inside dips_grid_cell(roi_w, roi_h, NULL, rows, cols, r, c).
+ * rows = cols = 1 is the count series of the mask, rows = roi_h and cols =
+ * roi_w the mask unpacked to u32.  Every entry is written.  n_frames == 0
+ * returns OK and writes nothing.  DIPS_ERR_INVALID, counts untouched: the
+ * grid errors of dips_grid_cell, roi_w or roi_h of 0, a region of 2^30 pixels
+ * or more, n_frames * rows * cols >= 2^30, a null pointer with n_frames > 0,
+ * a misaligned device pointer, counts overlapping mask.
+ *
+ * dips_mask_pixel_times: times (four planes of roi_w * roi_h u32 in exactly
+ * dips_diff_pixel_times' layout, the same fold with bit(t, j, i) the mask's
+ * bit and g = t0 + t, the same DIPS_TIMES_* and DIPS_TIME_NONE) and sums
+ * (sums[j*roi_w + i] = the number of frames whose bit is set, modulo 2^32)
+ * from one read of the mask.  Either output may be NULL, not both.
+ * accumulate == 0: the call starts from the initial state ({NONE, NONE, 0,
+ * 0}, sums 0) and overwrites (with n_frames == 0 it writes the initial
+ * state); accumulate != 0: the batch is folded onto what the outputs hold
+ * (nothing is written when n_frames == 0).  Any chunking of a clip gives,
+ * byte for byte, what one call gives, one frame per call and empty calls
+ * included; a run across a call boundary is counted whole.  DIPS_ERR_INVALID,
+ * the outputs untouched: both outputs null, a null mask with n_frames > 0,
+ * roi_w or roi_h of 0, a region of 2^30 pixels or more, times given and t0 +
+ * n_frames > 0xFFFFFFFF, a misaligned device pointer, an output overlapping
+ * the mask or the other output.
+ *
+ * Both: DIPS_FLAG_DEVICE_PTRS: the pointers are device pointers, 4-byte
+ * aligned, the call asynchronous on the handle's stream; else host pointers
+ * of any alignment, staged through HBM, synchronous, the state uploaded first
+ * when accumulating.  DIPS_FLAG_TIME_KERNEL: one entry for all launches of a
+ * call.  No scratch beyond the per-part summaries of a clip whose frames are
+ * cut into parts. */
+dips_status dips_mask_counts(dips_handle *h, const uint8_t *mask, uint32_t n_frames,
+                             uint32_t roi_w, uint32_t roi_h, uint32_t rows, uint32_t cols,
+                             uint32_t *counts);
+dips_status dips_mask_pixel_times(dips_handle *h, const uint8_t *mask, uint32_t n_frames,
+                                  uint32_t roi_w, uint32_t roi_h, uint32_t t0, uint32_t accumulate,
+                                  uint32_t *times, uint32_t *sums);
+
 /* Synthetic frames (shared integer generator, bit-identical to the oracle),
  * global frame indices t0 .. t0+n_frames-1, written to DEVICE memory `dst`. */
 dips_status dips_synth_frames(dips_handle *h, uint32_t width, uint32_t height,

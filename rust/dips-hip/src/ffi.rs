@@ -218,6 +218,10 @@ extern "C" {
                            shape: u32, rx: u32, ry: u32, mask_out: *mut u8) -> DipsStatus;
     pub fn dips_mask_vote(h: *mut DipsHandle, mask_in: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, window: u32,
                           votes: u32, history_in: *const u8, history_out: *mut u8, mask_out: *mut u8) -> DipsStatus;
+    pub fn dips_mask_counts(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, rows: u32,
+                            cols: u32, counts: *mut u32) -> DipsStatus;
+    pub fn dips_mask_pixel_times(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, t0: u32,
+                                 accumulate: u32, times: *mut u32, sums: *mut u32) -> DipsStatus;
     pub fn dips_synth_frames(h: *mut DipsHandle, width: u32, height: u32, seed: u64, t0: u64, n_frames: u32,
                              dst: *mut u8) -> DipsStatus;
     pub fn dips_kernel_time(h: *mut DipsHandle, total_ms: *mut f64, launches: *mut u64) -> DipsStatus;
