@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -172,6 +173,7 @@ dips_status dips_create(const dips_params* params, int device, dips_handle** out
         if (!h) return DIPS_ERR_NOMEM;
         h->p = p;
         h->device = device;
+        if (const char* scr = std::getenv("DIPS_SERIES_SCREEN")) h->series_screen = std::strtol(scr, nullptr, 10) != 0;
         e = hipSetDevice(device);
         if (e == hipSuccess) e = hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, device);
         // blocking: ordered with stream 0 (see dips_set_stream)

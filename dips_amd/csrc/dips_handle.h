@@ -124,6 +124,10 @@ struct dips_handle {
     const uint8_t* shard_last_ref = nullptr;  // the reference of the last sharded call's first frame
     uint64_t shard_last_bytes = 0;
 
+    // the screened form of the RGB8 series kernel (series_v2_screen.h);
+    // DIPS_SERIES_SCREEN=0 at dips_create switches it off
+    bool series_screen = true;
+
     bool crosscheck() const { return (p.flags & DIPS_FLAG_CROSSCHECK) != 0; }
 };
 

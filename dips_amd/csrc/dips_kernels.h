@@ -56,6 +56,7 @@ struct SeriesArgs {
     uint32_t n_tiles;
     uint32_t n_waves;
     float thr;               // threshold in kernel units: series_threshold()
+    uint32_t screen;         // screened series_v2 (series_v2_screen.h): series_screen_level(tau), >= 0 there
     const void* lut;         // GRAY8 table kernel: T_d / T_c bytes (series_gray.hip), 128 KiB
     uint32_t part_frames;    // frames per part of the part-major schedule (series_v2 SCHED = 1)
     // GRAY8 table kernel, layout 4: each workgroup samples its waves' first
@@ -635,7 +636,9 @@ inline bool alt_fast_epilogue_ok(uint32_t filter, float k) {
 int pixels_per_vec(int channels);
 int fast_unroll(int channels);
 // isi (series_v2, RGB8 / RGBA8): 0 the exact f64 intensity sum, 1 the
-// integer sum with a threshold select (ISI; needs tau >= 2^-5)
+// integer sum with a threshold select (ISI; needs tau >= 2^-5) -- for plain
+// aligned RGB8 its screened form (series_v2_screen.h; SeriesArgs::screen) --,
+// 3 the integer sum without the screen (as 1 where there is no screened form)
 const void* series_fast_kernel_ptr(int channels, int chroma, bool per_frame, bool map, bool align = false,
                                    int isi = 0);
 const void* series_v2_kernel_ptr(int channels, int chroma, bool per_frame, bool map, bool align = false,

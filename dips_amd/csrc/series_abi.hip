@@ -87,7 +87,7 @@ dips_status run_series_device(dips_handle* h, uint32_t width, uint32_t height, c
     // offset pointer) run the aligned-load form of the kernel (series_v2.hip
     // ALIGN)
     const bool align = (C == 3 || C == 4) && ((((uintptr_t)frames | (uintptr_t)fb | (uintptr_t)ref0) & 3u) != 0u);
-    const int isi = series_isi_form(h);
+    const int isi = series_v2_form(h);
     if (!(h->p.flags & DIPS_FLAG_FORCE_GENERIC))
         g = glut ? gray_lut_geometry(h, width, height, n_frames)
                  : fast_geometry(h, width, height, n_frames, C, pf, map != nullptr, align, isi);
@@ -150,6 +150,7 @@ dips_status run_series_device(dips_handle* h, uint32_t width, uint32_t height, c
         a.n_tiles = (uint32_t)g.n_tiles;
         a.n_waves = (uint32_t)g.n_waves;
         a.thr = dips::series_threshold(C, h->p.tau, isi);
+        a.screen = (uint32_t)std::max(0, dips::series_screen_level(h->p.tau));  // read by the screened form only
         a.part_frames = g.part_frames;  // 0: contiguous ranges (part_geometry)
         if (glut) {
             a.lut = h->gray_lut.p;
@@ -179,7 +180,7 @@ uint64_t series_waves(dips_handle* h, uint32_t width, uint32_t height, uint32_t 
     FastGeom g = C == 1 && gray_lut_enabled(h)
                      ? gray_lut_geometry(h, width, height, n_frames, env_cap)
                      : fast_geometry(h, width, height, n_frames, C, h->p.mode == DIPS_MODE_PER_FRAME, false, false,
-                                     series_isi_form(h), env_cap);
+                                     series_v2_form(h), env_cap);
     return g.ok ? g.n_waves : 0;
 }
 
@@ -379,7 +380,7 @@ dips_status dips_read_ceiling_walk(dips_handle* h, const uint8_t* dev_frames, ui
         // the geometry and schedule an aligned batch of this shape runs with
         // (part-major for batches of >= 256 frames, either mode)
         FastGeom g = fast_geometry(h, width, height, n_frames, C, h->p.mode == DIPS_MODE_PER_FRAME, false, false,
-                                   series_isi_form(h));
+                                   series_v2_form(h));
         if (!g.ok) return fail(h, DIPS_ERR_INVALID, "read_ceiling_walk: shape not eligible for the series kernel");
         dips::SeriesArgs a{};
         a.frames = dev_frames;
@@ -408,7 +409,7 @@ dips_status dips_series_geometry(dips_handle* h, uint32_t width, uint32_t height
         FastGeom g = C == 1 && gray_lut_enabled(h)
                          ? gray_lut_geometry(h, width, height, n_frames)
                          : fast_geometry(h, width, height, n_frames, C, h->p.mode == DIPS_MODE_PER_FRAME, false,
-                                         false, series_isi_form(h));
+                                         false, series_v2_form(h));
         if (waves) *waves = g.ok ? g.n_waves : 0;
         if (tiles) *tiles = g.ok ? g.n_tiles : 0;
         if (partial_bytes) *partial_bytes = g.ok ? g.n_tiles * 16u : 0;

@@ -11,6 +11,7 @@
 #include "dips_handle.h"
 #include "dips_kernels.h"
 #include "series_sched.h"
+#include "series_screen_rule.h"
 
 namespace dips_internal {
 
@@ -57,6 +58,14 @@ inline int series_isi_form(const dips_handle* h) {
     const int C = (int)h->p.format;
     if (C == 1 || h->crosscheck() || !dips::series_v2_isi(h->p.tau)) return 0;
     return 1;
+}
+
+// The form series_v2_kernel_ptr is asked for: series_isi_form, with the
+// integer sum as 3 (no screen, series_v2_screen.h) where the handle was
+// created with the screen switched off (DIPS_SERIES_SCREEN=0).
+inline int series_v2_form(const dips_handle* h) {
+    const int isi = series_isi_form(h);
+    return isi == 1 && !h->series_screen ? 3 : isi;
 }
 
 // Whether a regional product may run its fast kernel: GRAY8 has no fast

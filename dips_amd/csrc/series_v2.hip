@@ -26,8 +26,23 @@
 //    alternated runs on one box: +0.3-0.7 points (profiles/r05/ab_u5/);
 //    U = 2 at 8 waves and U = 3 at 6 had lost to U = 4 the same way;
 //  * the two frames of a pair are reduced together and their 8 wave sums are
-//    stored straight from the lanes that hold them (no v_readlane).
-#include "series_v2_frame.h"
+//    stored straight from the lanes that hold them (no v_readlane);
+//  * plain aligned RGB8, 'per-frame', tau >= 2^-5 (the bench's instantiation
+//    <3, 0, 5, true, false, false, 1>) runs the screened frame function of
+//    series_v2_screen.h: SAD and the integer SJ for every pixel, and the exact
+//    intensities only for the 256-pixel vec rows in which some pixel has
+//    |dJ| > s(tau) -- no other pixel can be selected (255 |dI2| = |dJ| + err,
+//    |err| < 1.1e-4; series_screen_rule.h, exhaustive in
+//    tests/test_screen_bound.py).  9.3 % of the bench content's rows hit
+//    (counted on the CPU); 118 VGPRs, no scratch, 7.35 VALU per pixel on the
+//    fast path against 13.65, 19.5 on a row that hits.  Measured on one
+//    resident 4K batch, forms alternated (tools/screen_ab.py,
+//    profiles/screen_ab/): 20.33 against 20.66 ms, +1.6 %, every screened
+//    round below every unscreened one; i.i.d. random frames, where every row
+//    hits, 32.3 against 20.7 ms.  DIPS_SERIES_SCREEN=0 at dips_create picks
+//    the unscreened body, kept as ISI = 3.  'overall' has no screened form
+//    (it spills, v2_screened below).
+#include "series_v2_screen.h"
 
 namespace dips {
 
@@ -38,6 +53,15 @@ namespace dips {
 template <int C, int U, bool PF, bool MAP, bool ALIGN = false>
 constexpr int v2_min_waves() {
     return ALIGN ? (MAP ? 1 : (U >= 5 ? 3 : 4)) : ((C == 3 && PF && !MAP) ? (U <= 2 ? 8 : (U == 3 ? 6 : (U == 4 ? 5 : 4))) : 1);
+}
+
+// Whether <C, CH, PF, MAP, ALIGN, ISI> is the screened form of the integer
+// sum (series_v2_screen.h): plain RGB8, 'per-frame'.  ('overall' keeps the
+// reference's bytes AND its J pairs beside the ring; hipcc 7 then spills --
+// 292 B of scratch at 4 waves per SIMD, 136 B at 3 -- so it stays unscreened.)
+template <int C, int CH, bool PF, bool MAP, bool ALIGN, int ISI>
+constexpr bool v2_screened() {
+    return ISI == 1 && C == 3 && CH == 0 && PF && !MAP && !ALIGN;
 }
 
 // The aligned-load form of an RGB8 vec (ALIGN): a frame whose base address
@@ -83,6 +107,11 @@ __device__ __forceinline__ void series_v2_body(const SeriesArgs& a) {
     static_assert(!ALIGN || C == 3 || C == 4, "the aligned-load form is the RGB8 / RGBA8 one");
     constexpr bool A4 = ALIGN && C == 4;  // RGBA8: the fifth dword from the next lane
     constexpr int LW = (ALIGN && C == 3) ? F::NDW + 1 : F::NDW;  // dwords loaded per vec
+    // ISI: 0 the exact f64 intensity sum, 1 the integer sum -- screened
+    // (series_v2_screen.h) where the variant has that form --, 3 the integer
+    // sum unscreened (frame_v2's ISI = 1)
+    constexpr bool SCR = v2_screened<C, CH, PF, MAP, ALIGN, ISI>();
+    constexpr int FISI = ISI != 0 ? 1 : 0;
     static_assert(U * 64 * F::VB <= 4096, "vec offsets must fit the 12-bit immediate");
     zero_series(a);
     const uint32_t lane = threadIdx.x & 63u;
@@ -164,7 +193,17 @@ __device__ __forceinline__ void series_v2_body(const SeriesArgs& a) {
         // reference bytes in rb
         uint32_t buf[4][U][LW];
         uint32_t rb[U][LW];  // overall mode only
-        St2 st[U];
+        St2 st[SCR ? 1 : U];
+        uint32_t jst[SCR ? U : 1][2];  // SCR: the reference's J pairs instead
+        ScreenLevel lv{};
+        if constexpr (SCR) lv = screen_level(a);
+        auto frame = [&](const uint32_t (&rv)[U][LW], const uint32_t (&cv)[U][LW], uint32_t tf, uint32_t* vals,
+                         uint32_t& cnt) __attribute__((always_inline)) {
+            if constexpr (SCR)
+                frame_v2_screen<U, PF>(a, lv, jst, rv, cv, vals, cnt);
+            else
+                frame_v2<C, CH, U, PF, MAP, SAUX, LW, LW, FISI>(a, st, rv, cv, voff, tf, vals, cnt);
+        };
         // ALIGN: the vec bytes of ring slot j in place (done once per frame, at
         // its first use; in 'per-frame' mode the slot then serves as the next
         // frame's reference as it is)
@@ -224,7 +263,10 @@ __device__ __forceinline__ void series_v2_body(const SeriesArgs& a) {
                 uint32_t dv[F::NDW];
 #pragma unroll
                 for (int k2 = 0; k2 < F::NDW; ++k2) dv[k2] = dref[u][k2];
-                derive_v2<C, CH, (ISI != 0)>(dv, st[u]);
+                if constexpr (SCR)
+                    derive_j(dv, jst[u]);
+                else
+                    derive_v2<C, CH, (ISI != 0)>(dv, st[u]);
             }
         }
 
@@ -239,14 +281,12 @@ __device__ __forceinline__ void series_v2_body(const SeriesArgs& a) {
                     const uint32_t tf = t0 + k + (uint32_t)j;
                     if constexpr (PF) {
                         settle((j + 1) & 3);
-                        frame_v2<C, CH, U, PF, MAP, SAUX, LW, LW, ISI>(a, st, buf[j], buf[(j + 1) & 3], voff, tf,
-                                                                  v + 4 * q, q ? c1 : c0);
+                        frame(buf[j], buf[(j + 1) & 3], tf, v + 4 * q, q ? c1 : c0);
                         __builtin_amdgcn_sched_barrier(0);
                         load_frame(tf + 3, buf[j], &sh[j], &tl[j]);
                     } else {
                         settle(j);
-                        frame_v2<C, CH, U, PF, MAP, SAUX, LW, LW, ISI>(a, st, rb, buf[j], voff, tf, v + 4 * q,
-                                                                  q ? c1 : c0);
+                        frame(rb, buf[j], tf, v + 4 * q, q ? c1 : c0);
                         __builtin_amdgcn_sched_barrier(0);
                         load_frame(tf + 4, buf[j], &sh[j], &tl[j]);
                     }
@@ -263,10 +303,10 @@ __device__ __forceinline__ void series_v2_body(const SeriesArgs& a) {
                 const uint32_t tf = t0 + k + (uint32_t)j;
                 if constexpr (PF) {
                     settle(j + 1);
-                    frame_v2<C, CH, U, PF, MAP, SAUX, LW, LW, ISI>(a, st, buf[j], buf[j + 1], voff, tf, v, c);
+                    frame(buf[j], buf[j + 1], tf, v, c);
                 } else {
                     settle(j);
-                    frame_v2<C, CH, U, PF, MAP, SAUX, LW, LW, ISI>(a, st, rb, buf[j], voff, tf, v, c);
+                    frame(rb, buf[j], tf, v, c);
                 }
                 const uint32_t y = wave_sum4_lanes(v);
                 store_one(rpart, tf, rec_off4, lane, y, c);
@@ -276,7 +316,8 @@ __device__ __forceinline__ void series_v2_body(const SeriesArgs& a) {
 }
 
 template <int C, int CH, int U, bool PF, bool MAP, bool ALIGN = false, int ISI = 0>
-__global__ __launch_bounds__(256, (v2_min_waves<C, U, PF, MAP, ALIGN>())) void series_v2_kernel(SeriesArgs a) {
+__global__ __launch_bounds__(256, (v2_screened<C, CH, PF, MAP, ALIGN, ISI>() ? 4 : v2_min_waves<C, U, PF, MAP, ALIGN>()))
+void series_v2_kernel(SeriesArgs a) {
     series_v2_body<C, CH, U, PF, MAP, kAuxNT, kAuxNT, 0, ALIGN, ISI>(a);
 }
 
@@ -306,6 +347,12 @@ static const void* pick_v2(int chroma, bool pf, bool map) {
 }
 
 const void* series_v2_kernel_ptr(int channels, int chroma, bool per_frame, bool map, bool align, int isi) {
+    // isi 3: the screened variants run their unscreened body, the others
+    // have one integer-sum form
+    if (isi == 3) {
+        if (channels == 3 && chroma == 0 && per_frame && !map && !align) return v2_ptr<3, 0, true, false, false, 3>();
+        isi = 1;
+    }
     switch (channels) {
         case 3:
             if (isi == 1)
