@@ -94,6 +94,18 @@ __device__ __forceinline__ float intensity_rgb(uint32_t r, uint32_t g, uint32_t 
     return (cmax + cmin) / 2.0f;
 }
 
+// The per-pixel body of the generic kernels: the intensity of the pixel whose
+// C bytes start at base[pb]; GRAY8 replicates its byte and takes no chroma
+// filter.
+template <int C>
+__device__ __forceinline__ float generic_intensity(const uint8_t* base, uint64_t pb, uint32_t chroma) {
+    uint32_t v[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int c = 0; c < (C < 3 ? C : 3); ++c) v[c] = base[pb + c];
+    if constexpr (C == 1) v[1] = v[2] = v[0];
+    return intensity_rgb(v[0], v[1], v[2], C == 1 ? 0u : chroma);
+}
+
 // Filter + sensitivity + colour epilogue of compute_main
 // (dips_shader.wgsl:213-239; map :97-105, sigmoid :108-112,
 // inv_sigmoid :114-118, diff_to_color :30-36, hsl_to_rgb :40-62).

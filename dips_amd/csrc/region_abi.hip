@@ -102,29 +102,14 @@ dips_status run_grid_device(dips_handle* h, uint32_t width, uint32_t height, con
         a.thr = dips::series_threshold(C, h->p.tau, isi);
         a.g = g;
         DIPS_HIP(h, dips::launch_series_grid(a, C, (int)h->p.chroma_filter, pf, isi, (uint32_t)q.blocks, s));
-        // the vecs the fast kernel leaves out (series_grid.hip): a partial
-        // last vec of a cell row that starts within 3 pixels of the frame's
-        // end would read past it.  A full vec ends inside its row, so these
-        // lie in the frame's last row, and in frames narrower than 3 pixels
-        // in up to three rows before it (the bound of series_sched.h
-        // for_frame_end_tail_rows, whose walk of one region's rows a grid of
-        // cells cannot use).  Their <= 3 pixels go into their cells by atomics
-        // (after the kernel's zeroing); cell edges decrease with the column,
-        // so at most three cells of a row qualify
-        const uint64_t npx = (uint64_t)width * height;
-        uint32_t crow = g.rows - 1u;  // the grid row of region row y
-        for (uint32_t y = g.y + g.h; y-- > g.y;) {
-            if (((uint64_t)y + 1u) * width + 3u <= npx) break;  // every vec of this and the earlier rows fits
-            while (dips::grid_cell_rect(g, crow, 0u).y > y) --crow;
-            for (uint32_t c = g.cols; c-- > 0;) {
-                const dips::GridRect rc = dips::grid_cell_rect(g, crow, c);
-                if ((uint64_t)y * width + rc.x + rc.w + 3u <= npx) break;  // so does every vec of the earlier columns
-                const uint32_t x0 = rc.x + ((rc.w - 1u) & ~3u);  // the cell row's last vec
-                if (rc.w % 4u == 0u || (uint64_t)y * width + x0 + 4u <= npx) continue;
-                const dips::GridSpec tail{x0, y, rc.x + rc.w - x0, 1u, 1u, 1u};
-                DIPS_TRY(launch_generic(tail, crow * g.cols + c));
-            }
-        }
+        // the vecs the fast kernel leaves out (series_grid.hip; the walk is
+        // series_sched.h for_grid_frame_end_tails): their <= 3 pixels go into
+        // their cells by atomics (after the kernel's zeroing)
+        DIPS_TRY(dips_sched::for_grid_frame_end_tails(
+            width, height, g.y, g.h, g.rows, g.cols, [&](uint32_t r, uint32_t c) { return dips::grid_cell_rect(g, r, c); },
+            [&](uint32_t crow, uint32_t c, uint32_t x0, uint32_t y, uint32_t n) {
+                return launch_generic(dips::GridSpec{x0, y, n, 1u, 1u, 1u}, crow * g.cols + c);
+            }));
     } else {
         DIPS_TRY(launch_generic(g, 0u));
     }

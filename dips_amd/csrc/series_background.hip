@@ -9,12 +9,9 @@
 // bit = 1.  One read of the batch; every mask word and every state value has
 // one final writer.
 //
-// The fast kernel takes series_mask_kernel's skeleton (series_mask.hip): the
-// words-out-of-nibbles geometry (a vec = 4 pixels of a region row, rows
-// padded to 8 vecs per mask word, a tile = 64 * U flat vecs, the 8 lanes of a
-// group own one word), per-slot offsets once per tile, raw buffer loads
-// through a wave-uniform descriptor, the 4-slot frame ring, the DPP OR and
-// one store per word.  What differs:
+// The fast kernel is the regional skeleton (series_region.h) as
+// series_mask_kernel uses it: word-padded slots, the frames-only ring, one
+// store per word.  What differs:
 //
 //   One part always.  The recurrence is sequential in t and truncating: a
 //   part cannot start without the state before it, so a wave owns every frame
@@ -38,8 +35,8 @@
 //   lane's 4 pixels are 8 contiguous bytes of a plane.  The pixels of a
 //   partial vec beyond the region's right edge are neither loaded nor stored.
 //
-// A partial vec that would read past the frame's end (series_mask.hip's off +
-// VB > frame_bytes test) is left out: the fast kernel stores neither its
+// A partial vec that would read past the frame's end (series_slots.h
+// vec_crosses_frame_end) is left out: the fast kernel stores neither its
 // pixels' state nor the mask word that holds it.  The generic kernel computes
 // that whole word and those pixels' state in an EARLIER launch of the stream
 // (run_background_device): it needs the initial state of all of the word's
@@ -47,7 +44,7 @@
 // overwrites.  The two launches write disjoint addresses.
 #include <algorithm>
 
-#include "series_v2_frame.h"
+#include "series_region.h"
 
 namespace dips {
 
@@ -134,11 +131,7 @@ __device__ __forceinline__ void frame_background(float thr, const BgRate& q, u16
                 st[u][c][k] = as_u16x2((as_u32(b) & keep[k]) | (as_u32(nb) & ~keep[k]));
             }
         }
-        uint32_t w = (nib << sh) & nm[u];
-        w |= DIPS_DPP(w, 0xB1);   // quad_perm [1,0,3,2]  (xor 1)
-        w |= DIPS_DPP(w, 0x4E);   // quad_perm [2,3,0,1]  (xor 2)
-        w |= DIPS_DPP(w, 0x141);  // row_half_mirror      (xor 7 inside 8 lanes)
-        word[u] = w;
+        word[u] = nibble_word(nib, sh, nm[u]);
     }
 }
 
@@ -147,8 +140,6 @@ __device__ __forceinline__ void frame_background(float thr, const BgRate& q, u16
 #ifndef DIPS_BG_WAVES
 #define DIPS_BG_WAVES 4
 #endif
-
-constexpr uint32_t kBgNone = 0x80000000u;  // an offset past every descriptor: loads give 0, stores are dropped
 
 template <int C, int CH, int U>
 __global__ __launch_bounds__(256, DIPS_BG_WAVES) void series_background_kernel(BgArgs a) {
@@ -160,7 +151,7 @@ __global__ __launch_bounds__(256, DIPS_BG_WAVES) void series_background_kernel(B
     const uint32_t fb = a.frame_bytes;
     const uint32_t mfb = a.mask_frame_bytes;
     const GridRect rc = a.roi;
-    const uint32_t vpr8 = ((rc.w + 31u) >> 5) << 3;  // vecs per padded region row
+    const uint32_t vpr8 = dips_sched::word_vpr(rc.w);  // vecs per padded region row
     const uint32_t nvec8 = vpr8 * rc.h;              // = mfb / 4 * 8
     const uint32_t sh = (lane & 7u) * 4u;
     const uint32_t plane_bytes = rc.w * rc.h * 2u;   // < 2^31 (the region stays below 2^30 pixels)
@@ -178,52 +169,25 @@ __global__ __launch_bounds__(256, DIPS_BG_WAVES) void series_background_kernel(B
     for (uint32_t tile = wave; tile < a.n_tiles; tile += a.n_waves) {
         const uint32_t v0 = tile * (uint32_t)(64 * U);
 
-        // per lane-slot, once per tile: the byte offset into a frame (kBgNone
-        // for a slot beyond the region's right edge or rows and for the vec
-        // that would cross the frame's end), the valid pixels of its nibble,
-        // the byte offset of its pixels in a state plane with their count
-        // (0: a slot that holds no state), and for the first lane of a group
-        // the byte offset of the group's word -- kBgNone when there is no
-        // mask or the word holds a vec that was left out
+        // per lane-slot, once per tile: where it loads from, the valid pixels
+        // of its nibble, the byte offset of its pixels in a state plane with
+        // their count (0: none), and for the first lane of a group the byte
+        // offset of the group's word -- kNoSlot when there is no mask or the
+        // word holds a vec that was left out
         uint32_t voff[U], nm[U], woff[U], soff[U], spx[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t idx = v0 + (uint32_t)(u * 64) + lane;
-            const uint32_t r = idx / vpr8;
-            const uint32_t x4 = (idx - r * vpr8) * 4u;
-            const bool in = idx < nvec8 && x4 < rc.w;
-            const uint32_t off = in ? ((rc.y + r) * a.width + rc.x + x4) * (uint32_t)C : 0u;
-            const bool ok = in && off + (uint32_t)F::VB <= fb;
-            voff[u] = ok ? off : kBgNone;
-            const uint32_t left = in ? min(4u, rc.w - x4) : 0u;
-            nm[u] = ((1u << left) - 1u) << sh;
-            spx[u] = ok ? left : 0u;
-            soff[u] = ok ? (r * rc.w + x4) * 2u : kBgNone;
-            uint32_t out = (in && !ok) ? 1u : 0u;
-            out |= DIPS_DPP(out, 0xB1);
-            out |= DIPS_DPP(out, 0x4E);
-            out |= DIPS_DPP(out, 0x141);
-            woff[u] = ((lane & 7u) == 0u && idx < nvec8 && out == 0u && a.mask != nullptr) ? (idx >> 3) * 4u : kBgNone;
+            const dips_sched::WordSlot q = dips_sched::region_word_slot(rc, vpr8, nvec8, a.width, (uint32_t)C, fb, idx);
+            voff[u] = q.voff;
+            nm[u] = dips_sched::slot_word_bits(q.left, sh);
+            spx[u] = q.ok ? q.left : 0u;
+            soff[u] = q.ok ? (q.r * rc.w + q.x4) * 2u : kNoSlot;
+            const uint32_t out = group8_or((q.in && !q.ok) ? 1u : 0u);  // by all lanes: no branch around it
+            woff[u] = ((lane & 7u) == 0u && idx < nvec8 && out == 0u && a.mask != nullptr) ? (idx >> 3) * 4u : kNoSlot;
         }
 
-        auto load_at = [&](const uint8_t* p, uint32_t (&dst)[U][NDW]) {
-            const __amdgpu_buffer_rsrc_t r = make_rsrc(p, fb);
-#pragma unroll
-            for (int u = 0; u < U; ++u) load_vec<C, kAuxNT>(r, voff[u], dst[u]);
-        };
-        auto load_frame = [&](uint32_t tf, uint32_t (&dst)[U][NDW]) {
-            load_at(a.frames + (uint64_t)min(tf, tlast) * fb, dst);
-        };
-        // words of frame tf: woff < mfb for every storing lane (idx < nvec8
-        // = 2 * mfb), the descriptor covers exactly this frame's mask
-        auto store_words = [&](uint32_t tf, const uint32_t (&word)[U]) {
-            const __amdgpu_buffer_rsrc_t r = make_rsrc(a.mask + (uint64_t)tf * mfb, a.mask != nullptr ? mfb : 0u);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (woff[u] != kBgNone) __builtin_amdgcn_raw_buffer_store_b32(word[u], r, woff[u], 0, 0);
-            }
-        };
-
+        const FrameLoader<C, U> ld{a.frames, fb, tlast, voff};
         // the initial state: what `background` holds, or 256 * the reference
         u16x2 st[U][C][2];
         uint32_t buf[4][U][NDW];
@@ -236,33 +200,17 @@ __global__ __launch_bounds__(256, DIPS_BG_WAVES) void series_background_kernel(B
                     make_rsrc(reinterpret_cast<const uint8_t*>(a.background) + (uint64_t)c * plane_bytes, plane_bytes);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    uint32_t lo = 0u, hi = 0u;
-                    if (spx[u] == 4u) {
-                        const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, soff[u], 0, 0);
-                        lo = v[0];
-                        hi = v[1];
-                    } else {
-                        if (spx[u] > 0u) lo = (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, soff[u], 0, 0);
-                        if (spx[u] > 1u)
-                            lo |= (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, soff[u] + 2u, 0, 0) << 16;
-                        if (spx[u] > 2u)
-                            hi = (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, soff[u] + 4u, 0, 0);
-                    }
+                    uint32_t lo, hi;
+                    load_state(r, soff[u], spx[u], lo, hi);
                     st[u][c][0] = as_u16x2(lo);
                     st[u][c][1] = as_u16x2(hi);
                 }
             }
-            load_frame(0u, buf[0]);
-            load_frame(1u, buf[1]);
-            load_frame(2u, buf[2]);
-            load_frame(3u, buf[3]);
+            ld.fill(0u, buf);
         } else {
             uint32_t rb[U][NDW];
-            load_at(a.ref0, rb);
-            load_frame(0u, buf[0]);
-            load_frame(1u, buf[1]);
-            load_frame(2u, buf[2]);
-            load_frame(3u, buf[3]);
+            ld.at(a.ref0, rb);
+            ld.fill(0u, buf);
             const u16x2 eight = {8, 8};
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -284,9 +232,9 @@ __global__ __launch_bounds__(256, DIPS_BG_WAVES) void series_background_kernel(B
                 const uint32_t tf = k + (uint32_t)j;
                 uint32_t word[U];
                 frame_background<C, CH, U>(a.thr, q, st, buf[j], nm, sh, word);
-                store_words(tf, word);
+                store_words<U>(a.mask + (uint64_t)tf * mfb, a.mask != nullptr ? mfb : 0u, woff, word);
                 __builtin_amdgcn_sched_barrier(0);
-                load_frame(tf + 4, buf[j]);
+                ld.frame(tf + 4, buf[j]);
             }
         }
         // tail: up to 3 frames, already in flight in their slots
@@ -295,7 +243,7 @@ __global__ __launch_bounds__(256, DIPS_BG_WAVES) void series_background_kernel(B
             if (k + (uint32_t)j < n) {
                 uint32_t word[U];
                 frame_background<C, CH, U>(a.thr, q, st, buf[j], nm, sh, word);
-                store_words(k + (uint32_t)j, word);
+                store_words<U>(a.mask + (uint64_t)(k + (uint32_t)j) * mfb, a.mask != nullptr ? mfb : 0u, woff, word);
             }
         }
 
@@ -383,21 +331,13 @@ __global__ __launch_bounds__(256) void background_generic_kernel(BgGenericArgs a
 // ---------------------------------------------------------------------------
 // Host-side launchers (instantiation table)
 // ---------------------------------------------------------------------------
-template <int C, int CH>
-static const void* background_ptr(bool small) {
-    return small ? reinterpret_cast<const void*>(&series_background_kernel<C, CH, 1>)
-                 : reinterpret_cast<const void*>(&series_background_kernel<C, CH, kUnrollBackground>);
-}
-
 template <int C>
 static const void* pick_background(int chroma, bool small) {
-    switch (chroma) {
-        case 0: return background_ptr<C, 0>(small);
-        case 1: return background_ptr<C, 1>(small);
-        case 2: return background_ptr<C, 2>(small);
-        case 3: return background_ptr<C, 3>(small);
-        default: return nullptr;
-    }
+    return dispatch_chroma(chroma, [&](auto ch) {
+        return dispatch_flag(small, [&](auto sm) {
+            return reinterpret_cast<const void*>(&series_background_kernel<C, ch.value, sm.value ? 1 : kUnrollBackground>);
+        });
+    });
 }
 
 const void* series_background_kernel_ptr(int channels, int chroma, bool small_tile) {

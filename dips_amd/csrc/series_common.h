@@ -153,6 +153,14 @@ __device__ __forceinline__ uint32_t group8_sum(uint32_t y) {
     return y;
 }
 
+// The OR over each 8-lane group, in all 8 lanes.
+__device__ __forceinline__ uint32_t group8_or(uint32_t w) {
+    w |= DIPS_DPP(w, 0xB1);   // quad_perm [1,0,3,2]  (xor 1)
+    w |= DIPS_DPP(w, 0x4E);   // quad_perm [2,3,0,1]  (xor 2)
+    w |= DIPS_DPP(w, 0x141);  // row_half_mirror      (xor 7 inside 8 lanes)
+    return w;
+}
+
 // Sum over the 64 lanes of in[v]; on return lanes 8v .. 8v+7 hold value v's
 // sum (every lane of that 8-lane group).
 __device__ __forceinline__ uint32_t wave_sum8_lanes(const uint32_t (&in)[8], uint32_t lane) {

@@ -6,10 +6,9 @@
 // rectangle.  Here a tile is 64 * U vecs of ONE cell (GridArgs,
 // dips_kernels.h): a vec is 4 horizontally consecutive pixels starting at
 // cell_x + 4 v in row cell_y + r, and the (row, vec-in-row) index is flattened
-// over the cell, so narrow cells still fill the lanes.  Each lane-slot's byte
-// offset into a frame is computed once per tile and kept in a register; the
-// loads are raw buffer loads through a wave-uniform descriptor over the whole
-// frame.  The per-pixel arithmetic is frame_v2 (series_v2_frame.h), unchanged:
+// over the cell, so narrow cells still fill the lanes: the flat slots of the
+// regional skeleton (series_slots.h, series_region.h), one cell at a time.
+// The per-pixel arithmetic is frame_v2 (series_v2_frame.h), unchanged:
 // same unroll, one call per (tile, frame), same 16-byte records.
 //
 // Masking.  The last vec of a cell row covers w % 4 valid pixels when that is
@@ -41,7 +40,7 @@
 // stride n_waves as in series_v2_body, a 4-slot register ring of frames (three
 // frames of loads in flight), one record per (tile, frame), summed per (cell,
 // frame) by grid_reduce_kernel.
-#include "series_v2_frame.h"
+#include "series_region.h"
 
 namespace dips {
 
@@ -63,8 +62,7 @@ constexpr int grid_min_waves() {
 
 template <int C, int CH, int U, bool PF, int ISI>
 __global__ __launch_bounds__(256, (grid_min_waves<C>())) void series_grid_kernel(GridArgs a) {
-    using F = Fmt<C>;
-    constexpr int NDW = F::NDW;
+    constexpr int NDW = Fmt<C>::NDW;
     if (a.zero != nullptr) {
         const uint32_t stride = gridDim.x * blockDim.x;
         for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < a.zero_n; j += stride) a.zero[j] = 0u;
@@ -77,55 +75,38 @@ __global__ __launch_bounds__(256, (grid_min_waves<C>())) void series_grid_kernel
     sa.thr = a.thr;
     // record dword offsets of the lanes that store reduced values; other
     // lanes point past the descriptor and their stores are dropped
-    const uint32_t rec_off8 = (lane & 7u) == 0u ? (lane >> 5) * 16u + ((lane >> 3) & 3u) * 4u : 0x80000000u;
-    const uint32_t rec_off4 = (lane & 15u) == 0u ? (lane >> 4) * 4u : 0x80000000u;
+    const uint32_t rec_off8 = (lane & 7u) == 0u ? (lane >> 5) * 16u + ((lane >> 3) & 3u) * 4u : kNoSlot;
+    const uint32_t rec_off4 = (lane & 15u) == 0u ? (lane >> 4) * 4u : kNoSlot;
 
-    const uint32_t plen = a.part_frames;
-    const uint64_t pitems = (uint64_t)((a.n_frames + plen - 1) / plen) * a.n_tiles;
+    const uint64_t pitems = region_items(a.n_frames, a.part_frames, a.n_tiles);
     for (uint64_t it = wave; it < pitems; it += a.n_waves) {
-        const uint32_t part = (uint32_t)(it / a.n_tiles);
-        const uint32_t tile = (uint32_t)(it - (uint64_t)part * a.n_tiles);
+        const RegionItem i = region_item(it, a.n_frames, a.part_frames, a.n_tiles);
+        const uint32_t tile = i.tile, t0 = i.t0, n = i.n;
         const uint32_t cell = tile / a.tiles_per_cell;
         const uint32_t v0 = (tile - cell * a.tiles_per_cell) * (uint32_t)(64 * U);
         const uint32_t crow = cell / a.g.cols;
         const GridRect rc = grid_cell_rect(a.g, crow, cell - crow * a.g.cols);
-        const uint32_t vpr = (rc.w + 3u) >> 2;  // vecs per cell row
+        const uint32_t vpr = dips_sched::flat_vpr(rc.w);  // vecs per cell row
         const uint32_t nvec = vpr * rc.h;
         if (v0 >= nvec) continue;  // a tile id past this cell's last tile
-        const uint32_t t0 = part * plen;
-        const uint32_t tend = min(a.n_frames, t0 + plen);
-        const uint32_t n = tend - t0;  // frames of this item (>= 1)
-        const uint32_t tlast = tend - 1;
 
-        // per lane-slot, once per tile: the byte offset into a frame and the
-        // byte mask of its valid pixels (all ones for a slot past the cell,
-        // whose loads return zeros)
+        // per lane-slot, once per tile: the frame offset and the byte mask of
+        // its valid pixels (all ones for a slot that loads nothing)
         uint32_t voff[U];
         uint32_t msk[U][NDW];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const uint32_t idx = v0 + (uint32_t)(u * 64) + lane;
-            const uint32_t r = idx / vpr;
-            const uint32_t x4 = (idx - r * vpr) * 4u;
-            const uint32_t off = ((rc.y + r) * a.width + rc.x + x4) * (uint32_t)C;
-            // the frame's last partial vec would cross its end: left to the host
-            const bool ok = idx < nvec && off + (uint32_t)F::VB <= fb;
-            const uint32_t nb = (ok ? min(rc.w - x4, 4u) : 4u) * (uint32_t)C;
-            voff[u] = ok ? off : 0x80000000u;
+            const dips_sched::Slot s =
+                dips_sched::region_slot(rc, vpr, nvec, a.width, (uint32_t)C, fb, v0 + (uint32_t)(u * 64) + lane);
+            const uint32_t nb = (s.ok ? dips_sched::vec_px_inside(rc.w, s.x4) : 4u) * (uint32_t)C;
+            voff[u] = s.voff;
 #pragma unroll
             for (int k = 0; k < NDW; ++k) msk[u][k] = head_mask(nb, k);
         }
+        const FrameLoader<C, U> ld{a.frames, fb, i.tlast, voff};
 
         const __amdgpu_buffer_rsrc_t rpart =
             make_rsrc(a.partials + 2 * (uint64_t)tile * a.n_frames, a.n_frames * 16u);
-        auto load_at = [&](const uint8_t* p, uint32_t (&dst)[U][NDW]) {
-            const __amdgpu_buffer_rsrc_t r = make_rsrc(p, fb);
-#pragma unroll
-            for (int u = 0; u < U; ++u) load_vec<C, kAuxNT>(r, voff[u], dst[u]);
-        };
-        auto load_frame = [&](uint32_t tf, uint32_t (&dst)[U][NDW]) {
-            load_at(a.frames + (uint64_t)min(tf, tlast) * fb, dst);
-        };
         // the mask pass of one ring slot (or the reference), in place
         auto settle = [&](uint32_t (&v)[U][NDW]) {
 #pragma unroll
@@ -135,26 +116,13 @@ __global__ __launch_bounds__(256, (grid_min_waves<C>())) void series_grid_kernel
             }
         };
 
-        // ring: PF -- frame k of the item in slot (k+1)&3, its reference
-        // (frame k-1) in slot k&3; overall -- frame k in slot k&3, the fixed
-        // reference bytes in rb
+        // the ring that also holds the reference bytes (ref_ring_fill); the
+        // loop pairs two frames per cross-lane reduction
         uint32_t buf[4][U][NDW];
         uint32_t rb[U][NDW];  // overall mode only
         St2 st[U];
         {
-            const uint8_t* rp = PF ? (t0 == 0 ? a.ref0 : a.frames + (uint64_t)(t0 - 1) * fb) : a.ref0;
-            uint32_t (&dref)[U][NDW] = PF ? buf[0] : rb;
-            load_at(rp, dref);
-            if constexpr (PF) {
-                load_frame(t0, buf[1]);
-                load_frame(t0 + 1, buf[2]);
-                load_frame(t0 + 2, buf[3]);
-            } else {
-                load_frame(t0, buf[0]);
-                load_frame(t0 + 1, buf[1]);
-                load_frame(t0 + 2, buf[2]);
-                load_frame(t0 + 3, buf[3]);
-            }
+            auto& dref = ref_ring_fill<PF>(ld, region_ref<PF>(a.frames, a.ref0, t0, fb), t0, buf, rb);
             settle(dref);
 #pragma unroll
             for (int u = 0; u < U; ++u) derive_v2<C, CH, (ISI != 0)>(dref[u], st[u]);
@@ -174,13 +142,13 @@ __global__ __launch_bounds__(256, (grid_min_waves<C>())) void series_grid_kernel
                         frame_v2<C, CH, U, PF, false, kAuxNT, NDW, NDW, ISI>(sa, st, buf[j], buf[(j + 1) & 3], 0u, tf,
                                                                             v + 4 * q, q ? c1 : c0);
                         __builtin_amdgcn_sched_barrier(0);
-                        load_frame(tf + 3, buf[j]);
+                        ld.frame(tf + 3, buf[j]);
                     } else {
                         settle(buf[j]);
                         frame_v2<C, CH, U, PF, false, kAuxNT, NDW, NDW, ISI>(sa, st, rb, buf[j], 0u, tf, v + 4 * q,
                                                                             q ? c1 : c0);
                         __builtin_amdgcn_sched_barrier(0);
-                        load_frame(tf + 4, buf[j]);
+                        ld.frame(tf + 4, buf[j]);
                     }
                 }
                 const uint32_t y = wave_sum8_lanes(v, lane);
@@ -341,20 +309,13 @@ __global__ __launch_bounds__(256) void grid_generic_kernel(GridGenericArgs a) {
 // ---------------------------------------------------------------------------
 // Host-side launchers (instantiation table)
 // ---------------------------------------------------------------------------
-template <int C, int CH, bool PF, int ISI>
-static const void* grid_ptr() {
-    return reinterpret_cast<const void*>(&series_grid_kernel<C, CH, v2_unroll<C>(), PF, ISI>);
-}
-
 template <int C, int ISI>
 static const void* pick_grid(int chroma, bool pf) {
-    switch (chroma) {
-        case 0: return pf ? grid_ptr<C, 0, true, ISI>() : grid_ptr<C, 0, false, ISI>();
-        case 1: return pf ? grid_ptr<C, 1, true, ISI>() : grid_ptr<C, 1, false, ISI>();
-        case 2: return pf ? grid_ptr<C, 2, true, ISI>() : grid_ptr<C, 2, false, ISI>();
-        case 3: return pf ? grid_ptr<C, 3, true, ISI>() : grid_ptr<C, 3, false, ISI>();
-        default: return nullptr;
-    }
+    return dispatch_chroma(chroma, [&](auto ch) {
+        return dispatch_flag(pf, [&](auto p) {
+            return reinterpret_cast<const void*>(&series_grid_kernel<C, ch.value, v2_unroll<C>(), p.value, ISI>);
+        });
+    });
 }
 
 const void* series_grid_kernel_ptr(int channels, int chroma, bool per_frame, int isi) {

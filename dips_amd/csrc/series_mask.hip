@@ -4,43 +4,35 @@
 // padded to whole words with zero bits.  One read of the batch, every word
 // written exactly once.
 //
-// The fast kernel takes series_pixels_kernel's skeleton: a persistent grid,
-// items (frame part, tile), per-slot byte offsets computed once per tile, raw
-// buffer loads through a wave-uniform descriptor over the whole frame, the
-// 4-slot frame ring and derive_v2.  Per frame it does derive_v2, the subtract
-// and the compare: no SAD, SJ, SI, no accumulator; only the reference state
-// crosses frames, so the ring holds frames alone in both modes (the reference
-// bytes are dropped once their state is derived).
+// The fast kernel is the regional skeleton (series_region.h) over the
+// word-padded slots with the frames-only ring (the slot decode is
+// series_slots.h region_word_slot's, written out: DESIGN.md).  Per frame it
+// does derive_v2, the subtract and the compare: no SAD, SJ, SI, no
+// accumulator; only the reference state crosses frames (the reference bytes
+// are dropped once their state is derived).
 //
 // One intensity form serves every tau: only the compare matters, and
 // |dI2s| > tau * 2^23 in the I2s = 2 I * 2^22 domain is an exact power-of-two
 // scaling of the reference's f32 compare for any tau (the x32 form exists for
 // the integer intensity sum, which the mask does not have).
 //
-// Geometry.  A vec is 4 horizontally consecutive pixels of one region row, so
-// a lane produces a nibble.  The vecs of a region row are padded to a
-// multiple of 8, vpr8 = 8 * ceil(w / 32), and (row, vec) is flattened over
-// vpr8 * h: 8 consecutive flat vecs starting at a multiple of 8 are the 32
-// pixels of one mask word of one row, and flat word i >> 3 is that word's
-// index in the frame's mask.  A tile is 64 * U flat vecs and a lane-slot holds
-// flat vec v0 + 64 u + lane, so the 8 lanes of a group (lane >> 3) always own
-// one word: the nibbles, shifted to their place, are ORed across lane ^ 1,
-// lane ^ 2 and the 8-lane mirror (DPP, no LDS) and the group's first lane
-// stores the word.  Every word of every frame is written by exactly one wave:
-// no atomics, no memset, any number of frame parts.  Slots past the region's
+// Words.  A lane produces a nibble; a tile is 64 * U flat vecs and a
+// lane-slot holds flat vec v0 + 64 u + lane, so the 8 lanes of a group
+// (lane >> 3) always own one word: the nibbles, shifted to their place, are
+// ORed across the group (DPP, no LDS) and the group's first lane stores the
+// word.  Every word of every frame is written by exactly one wave: no
+// atomics, no memset, any number of frame parts.  Slots past the region's
 // right edge inside the padded row load nothing (zeros against zeros: the
 // strict compare gives 0), the pixels of a partial vec beyond the edge are
 // masked out of the nibble, so the pad bits are 0.
 //
-// A partial vec that would read past the frame's end (the last vec of the
-// frame's last row; in frames narrower than 3 pixels that of up to three rows
-// before it) loads nothing either, and its bits come out 0 here; the host
-// then has the generic kernel recompute and store the whole word that holds
-// it, in a later launch of the same stream (run_mask_device applies the same
-// test).
+// A vec left out at the frame's end loads nothing either, and its bits come
+// out 0 here; the host then has the generic kernel recompute and store the
+// whole word that holds it, in a later launch of the same stream
+// (run_mask_device, by for_frame_end_tail_rows).
 #include <algorithm>
 
-#include "series_v2_frame.h"
+#include "series_region.h"
 
 namespace dips {
 
@@ -68,11 +60,7 @@ __device__ __forceinline__ void frame_mask(float thr, St2 (&st)[U], const uint32
             nib |= (fabsf(d.x) > thr ? 1u : 0u) << (2 * k);
             nib |= (fabsf(d.y) > thr ? 1u : 0u) << (2 * k + 1);
         }
-        uint32_t w = (nib << sh) & nm[u];
-        w |= DIPS_DPP(w, 0xB1);   // quad_perm [1,0,3,2]  (xor 1)
-        w |= DIPS_DPP(w, 0x4E);   // quad_perm [2,3,0,1]  (xor 2)
-        w |= DIPS_DPP(w, 0x141);  // row_half_mirror      (xor 7 inside 8 lanes)
-        word[u] = w;
+        word[u] = nibble_word(nib, sh, nm[u]);
         if constexpr (PF) st[u] = n;
     }
 }
@@ -85,116 +73,80 @@ __device__ __forceinline__ void frame_mask(float thr, St2 (&st)[U], const uint32
 
 template <int C, int CH, int U, bool PF>
 __global__ __launch_bounds__(256, DIPS_MASK_WAVES) void series_mask_kernel(MaskArgs a) {
-    using F = Fmt<C>;
-    constexpr int NDW = F::NDW;
+    constexpr int NDW = Fmt<C>::NDW;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= a.n_waves) return;
     const uint32_t fb = a.frame_bytes;
     const uint32_t mfb = a.mask_frame_bytes;
-    const GridRect rc = a.roi;
-    const uint32_t vpr8 = ((rc.w + 31u) >> 5) << 3;  // vecs per padded region row
-    const uint32_t nvec8 = vpr8 * rc.h;              // = mfb / 4 * 8
     const uint32_t sh = (lane & 7u) * 4u;
+    const uint32_t vpr8 = dips_sched::word_vpr(a.roi.w);  // vecs per padded region row
+    const uint32_t nvec8 = vpr8 * a.roi.h;                // = mfb / 4 * 8
 
-    const uint32_t plen = a.part_frames;
-    const uint64_t pitems = (uint64_t)((a.n_frames + plen - 1) / plen) * a.n_tiles;
+    const uint64_t pitems = region_items(a.n_frames, a.part_frames, a.n_tiles);
     for (uint64_t it = wave; it < pitems; it += a.n_waves) {
-        const uint32_t part = (uint32_t)(it / a.n_tiles);
-        const uint32_t tile = (uint32_t)(it - (uint64_t)part * a.n_tiles);
-        const uint32_t v0 = tile * (uint32_t)(64 * U);
-        const uint32_t t0 = part * plen;
-        const uint32_t tend = min(a.n_frames, t0 + plen);
-        const uint32_t n = tend - t0;  // frames of this item (>= 1)
-        const uint32_t tlast = tend - 1;
-
-        // per lane-slot, once per tile: the byte offset into a frame (past
-        // the descriptor for a slot beyond the region's right edge or rows,
-        // or the one vec that would cross the frame's end: its loads return
-        // zeros), the valid pixels of its nibble, and for the first lane of a
-        // group inside the mask the byte offset of the group's word
+        const RegionItem i = region_item(it, a.n_frames, a.part_frames, a.n_tiles);
+        // per lane-slot, once per tile: the frame offset, the valid pixels
+        // of its nibble in the word, the word's byte offset in a frame's mask
         uint32_t voff[U], nm[U], woff[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const uint32_t idx = v0 + (uint32_t)(u * 64) + lane;
+            const uint32_t idx = i.tile * (uint32_t)(64 * U) + (uint32_t)(u * 64) + lane;
             const uint32_t r = idx / vpr8;
             const uint32_t x4 = (idx - r * vpr8) * 4u;
-            const bool in = idx < nvec8 && x4 < rc.w;
-            const uint32_t off = in ? ((rc.y + r) * a.width + rc.x + x4) * (uint32_t)C : 0u;
-            const bool ok = in && off + (uint32_t)F::VB <= fb;
-            voff[u] = ok ? off : 0x80000000u;
-            const uint32_t left = in ? min(4u, rc.w - x4) : 0u;
-            nm[u] = ((1u << left) - 1u) << sh;
-            woff[u] = ((lane & 7u) == 0u && idx < nvec8) ? (idx >> 3) * 4u : 0x80000000u;
+            const bool in = idx < nvec8 && x4 < a.roi.w;
+            const uint32_t off = in ? ((a.roi.y + r) * a.width + a.roi.x + x4) * (uint32_t)C : 0u;
+            const bool cross = dips_sched::vec_crosses_frame_end(off, (uint32_t)Fmt<C>::VB, fb);
+            const bool ok = in && !cross;
+            voff[u] = ok ? off : kNoSlot;
+            const uint32_t left = in ? min(4u, a.roi.w - x4) : 0u;
+            nm[u] = dips_sched::slot_word_bits(left, sh);
+            woff[u] = ((lane & 7u) == 0u && idx < nvec8) ? (idx >> 3) * 4u : kNoSlot;
         }
+        const FrameLoader<C, U> ld{a.frames, fb, i.tlast, voff};
 
-        auto load_at = [&](const uint8_t* p, uint32_t (&dst)[U][NDW]) {
-            const __amdgpu_buffer_rsrc_t r = make_rsrc(p, fb);
-#pragma unroll
-            for (int u = 0; u < U; ++u) load_vec<C, kAuxNT>(r, voff[u], dst[u]);
-        };
-        auto load_frame = [&](uint32_t tf, uint32_t (&dst)[U][NDW]) {
-            load_at(a.frames + (uint64_t)min(tf, tlast) * fb, dst);
-        };
-        // words of frame tf: woff < mfb for every storing lane (idx < nvec8
-        // = 2 * mfb), the descriptor covers exactly this frame's mask
-        auto store_words = [&](uint32_t tf, const uint32_t (&word)[U]) {
-            const __amdgpu_buffer_rsrc_t r = make_rsrc(a.mask + (uint64_t)tf * mfb, mfb);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (woff[u] != 0x80000000u) __builtin_amdgcn_raw_buffer_store_b32(word[u], r, woff[u], 0, 0);
-            }
-        };
-
-        // ring: frame k of the item in slot k & 3; the reference (the frame
-        // before the part in per-frame mode) only leaves its state
+        // the reference only leaves its state
         uint32_t buf[4][U][NDW];
         St2 st[U];
         {
-            const uint8_t* rp = PF ? (t0 == 0 ? a.ref0 : a.frames + (uint64_t)(t0 - 1) * fb) : a.ref0;
             uint32_t rb[U][NDW];
-            load_at(rp, rb);
-            load_frame(t0, buf[0]);
-            load_frame(t0 + 1, buf[1]);
-            load_frame(t0 + 2, buf[2]);
-            load_frame(t0 + 3, buf[3]);
+            ld.at(region_ref<PF>(a.frames, a.ref0, i.t0, fb), rb);
+            ld.fill(i.t0, buf);
 #pragma unroll
             for (int u = 0; u < U; ++u) derive_v2<C, CH, false>(rb[u], st[u]);
         }
-
+        // ring: frame k of the item in slot k & 3
+        auto step = [&](const uint32_t (&cur)[U][NDW], uint32_t tf) {
+            uint32_t word[U];
+            frame_mask<C, CH, U, PF>(a.thr, st, cur, nm, sh, word);
+            store_words<U>(a.mask + (uint64_t)tf * mfb, mfb, woff, word);
+        };
         uint32_t k = 0;
-        for (; k + 4 <= n; k += 4) {
+        for (; k + 4 <= i.n; k += 4) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const uint32_t tf = t0 + k + (uint32_t)j;
-                uint32_t word[U];
-                frame_mask<C, CH, U, PF>(a.thr, st, buf[j], nm, sh, word);
-                store_words(tf, word);
+                const uint32_t tf = i.t0 + k + (uint32_t)j;
+                step(buf[j], tf);
                 __builtin_amdgcn_sched_barrier(0);
-                load_frame(tf + 4, buf[j]);
+                ld.frame(tf + 4, buf[j]);
             }
         }
         // tail: up to 3 frames, already in flight in their slots
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            if (k + (uint32_t)j < n) {
-                uint32_t word[U];
-                frame_mask<C, CH, U, PF>(a.thr, st, buf[j], nm, sh, word);
-                store_words(t0 + k + (uint32_t)j, word);
-            }
+            if (k + (uint32_t)j < i.n) step(buf[j], i.t0 + k + (uint32_t)j);
         }
     }
 }
 
 // Generic path: any format, shape and alignment.  One thread per (frame, mask
 // word) of a rectangle of words evaluates the word's up to 32 pixels with
-// series_generic_kernel's per-pixel body (the reference's own (cmax + cmin)
-// / 2 intensity form, dips_shader.wgsl:73-81; the previous frame read as the
-// reference in per-frame mode) and stores the word, pad bits 0.  It serves
-// GRAY8, DIPS_FLAG_FORCE_GENERIC, DIPS_FLAG_CROSSCHECK, the shapes the fast
-// kernel's geometry refuses and the words that hold a vec it leaves out;
-// being independent of derive_v2 it is the fast kernel's on-device
-// cross-check.
+// series_generic_kernel's per-pixel body (generic_intensity; the previous
+// frame read as the reference in per-frame mode) and stores the word, pad
+// bits 0.  It serves GRAY8, DIPS_FLAG_FORCE_GENERIC, DIPS_FLAG_CROSSCHECK,
+// the shapes the fast kernel's geometry refuses and the words that hold a vec
+// it leaves out; being independent of derive_v2 it is the fast kernel's
+// on-device cross-check.
 template <int C>
 __global__ __launch_bounds__(256) void mask_generic_kernel(MaskGenericArgs a) {
     uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -212,18 +164,8 @@ __global__ __launch_bounds__(256) void mask_generic_kernel(MaskGenericArgs a) {
     uint32_t bits = 0u;
     for (uint32_t b = 0; b < cnt; ++b) {
         const uint64_t pb = pb0 + (uint64_t)b * C;
-        uint32_t fv[4] = {0, 0, 0, 0}, rv[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            fv[c] = Fp[pb + c];
-            rv[c] = Rp[pb + c];
-        }
-        if constexpr (C == 1) {
-            fv[1] = fv[2] = fv[0];
-            rv[1] = rv[2] = rv[0];
-        }
-        const float If = intensity_rgb(fv[0], fv[1], fv[2], a.chroma);
-        const float Ir = intensity_rgb(rv[0], rv[1], rv[2], a.chroma);
+        const float If = generic_intensity<C>(Fp, pb, a.chroma);
+        const float Ir = generic_intensity<C>(Rp, pb, a.chroma);
         if (fabsf(If - Ir) > a.tau) bits |= 1u << b;
     }
     const uint32_t wpr = (a.roi.w + 31u) >> 5;
@@ -234,20 +176,13 @@ __global__ __launch_bounds__(256) void mask_generic_kernel(MaskGenericArgs a) {
 // ---------------------------------------------------------------------------
 // Host-side launchers (instantiation table)
 // ---------------------------------------------------------------------------
-template <int C, int CH, bool PF>
-static const void* mask_ptr() {
-    return reinterpret_cast<const void*>(&series_mask_kernel<C, CH, kUnrollMask, PF>);
-}
-
 template <int C>
 static const void* pick_mask(int chroma, bool pf) {
-    switch (chroma) {
-        case 0: return pf ? mask_ptr<C, 0, true>() : mask_ptr<C, 0, false>();
-        case 1: return pf ? mask_ptr<C, 1, true>() : mask_ptr<C, 1, false>();
-        case 2: return pf ? mask_ptr<C, 2, true>() : mask_ptr<C, 2, false>();
-        case 3: return pf ? mask_ptr<C, 3, true>() : mask_ptr<C, 3, false>();
-        default: return nullptr;
-    }
+    return dispatch_chroma(chroma, [&](auto ch) {
+        return dispatch_flag(pf, [&](auto p) {
+            return reinterpret_cast<const void*>(&series_mask_kernel<C, ch.value, kUnrollMask, p.value>);
+        });
+    });
 }
 
 const void* series_mask_kernel_ptr(int channels, int chroma, bool per_frame) {

@@ -2,17 +2,12 @@
 // region of interest (dips_diff_pixel_sums): one read of the batch, one entry
 // per pixel, written once.
 //
-// The fast kernel takes series_grid.hip's tile addressing with one cell equal
-// to the region: a tile is 64 * U vecs, a vec 4 horizontally consecutive
-// pixels of one region row (the last vec of a row may hold fewer), the
-// (row, vec-in-row) index flattened over the region.  Each lane-slot's byte
-// offset into a frame is computed once per tile; the loads are raw buffer
-// loads through a wave-uniform descriptor over the whole frame.  A wave keeps
-// its tile fixed and walks the frames of its part through the 4-slot register
-// ring of series_grid_kernel; derive_v2 and the 2^22-scaled intensity domain
-// are those of frame_v2.  What differs is the per-frame step (frame_pix
-// below): nothing is reduced across lanes, every pixel has its own
-// accumulators, and they live across the frames of the part.
+// The fast kernel is the regional skeleton (series_region.h) over the flat
+// slots of the region (series_slots.h region_slot) with the ring that holds
+// the reference bytes; derive_v2 and the 2^22-scaled intensity domain are
+// those of frame_v2.  Its own is the per-frame step (frame_pix below): nothing
+// is reduced across lanes, every pixel has its own accumulators, and they
+// live across the frames of the part.
 //
 // Accumulators, per pixel (4 VGPRs; 16 per vec):
 //   sad   u32: <= 1020 per frame, exact for 2^22 frames;
@@ -34,7 +29,7 @@
 // Only a partial vec that would read past the frame's end is left out: the
 // last vec of the frame's last row, and in frames narrower than 3 pixels
 // that of up to three rows before it; the host gives the <= 3 pixels of each
-// to the generic kernel (run_pixels_device applies the same test).
+// to the generic kernel (run_pixels_device, by for_frame_end_tail_rows).
 //
 // Schedule: a persistent grid, items (frame part, tile) dealt part-major with
 // stride n_waves.  With one part a wave owns every frame of its pixels and
@@ -42,7 +37,7 @@
 // accumulates); with several parts every part adds its share with u64
 // atomics, the host having zeroed the map in an earlier launch when the call
 // does not accumulate.
-#include "series_v2_frame.h"
+#include "series_region.h"
 
 namespace dips {
 
@@ -134,39 +129,21 @@ __global__ __launch_bounds__(256, (pix_min_waves<U>())) void series_pixels_kerne
     const uint32_t vpr = (rc.w + 3u) >> 2;  // vecs per region row
     const uint32_t nvec = vpr * rc.h;
 
-    const uint32_t plen = a.part_frames;
-    const uint64_t pitems = (uint64_t)((a.n_frames + plen - 1) / plen) * a.n_tiles;
+    const uint64_t pitems = region_items(a.n_frames, a.part_frames, a.n_tiles);
     for (uint64_t it = wave; it < pitems; it += a.n_waves) {
-        const uint32_t part = (uint32_t)(it / a.n_tiles);
-        const uint32_t tile = (uint32_t)(it - (uint64_t)part * a.n_tiles);
-        const uint32_t v0 = tile * (uint32_t)(64 * U);
-        const uint32_t t0 = part * plen;
-        const uint32_t tend = min(a.n_frames, t0 + plen);
-        const uint32_t n = tend - t0;  // frames of this item (>= 1)
-        const uint32_t tlast = tend - 1;
+        const RegionItem i = region_item(it, a.n_frames, a.part_frames, a.n_tiles);
+        const uint32_t t0 = i.t0, n = i.n, tlast = i.tlast;
+        const uint32_t v0 = i.tile * (uint32_t)(64 * U);
 
-        // per lane-slot, once per tile: the byte offset into a frame (past
-        // the descriptor for a slot beyond the region or the one vec that
-        // would cross the frame's end: its loads return zeros)
+        // per lane-slot, once per tile: where it loads from (series_slots.h)
         uint32_t voff[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const uint32_t idx = v0 + (uint32_t)(u * 64) + lane;
-            const uint32_t r = idx / vpr;
-            const uint32_t x4 = (idx - r * vpr) * 4u;
-            const uint32_t off = ((rc.y + r) * a.width + rc.x + x4) * (uint32_t)C;
-            const bool ok = idx < nvec && off + (uint32_t)F::VB <= fb;
-            voff[u] = ok ? off : 0x80000000u;
+            voff[u] =
+                dips_sched::region_slot(rc, vpr, nvec, a.width, (uint32_t)C, fb, v0 + (uint32_t)(u * 64) + lane).voff;
         }
 
-        auto load_at = [&](const uint8_t* p, uint32_t (&dst)[U][NDW]) {
-            const __amdgpu_buffer_rsrc_t r = make_rsrc(p, fb);
-#pragma unroll
-            for (int u = 0; u < U; ++u) load_vec<C, kAuxNT>(r, voff[u], dst[u]);
-        };
-        auto load_frame = [&](uint32_t tf, uint32_t (&dst)[U][NDW]) {
-            load_at(a.frames + (uint64_t)min(tf, tlast) * fb, dst);
-        };
+        const FrameLoader<C, U> ld{a.frames, fb, tlast, voff};
 
         // ring: PF -- frame k of the item in slot (k+1)&3, its reference
         // (frame k-1) in slot k&3; overall -- frame k in slot k&3, the fixed
@@ -185,19 +162,8 @@ __global__ __launch_bounds__(256, (pix_min_waves<U>())) void series_pixels_kerne
             }
         }
         {
-            const uint8_t* rp = PF ? (t0 == 0 ? a.ref0 : a.frames + (uint64_t)(t0 - 1) * fb) : a.ref0;
-            uint32_t (&dref)[U][NDW] = PF ? buf[0] : rb;
-            load_at(rp, dref);
-            if constexpr (PF) {
-                load_frame(t0, buf[1]);
-                load_frame(t0 + 1, buf[2]);
-                load_frame(t0 + 2, buf[3]);
-            } else {
-                load_frame(t0, buf[0]);
-                load_frame(t0 + 1, buf[1]);
-                load_frame(t0 + 2, buf[2]);
-                load_frame(t0 + 3, buf[3]);
-            }
+            const uint8_t* rp = region_ref<PF>(a.frames, a.ref0, t0, fb);
+            auto& dref = ref_ring_fill<PF>(ld, rp, t0, buf, rb);
 #pragma unroll
             for (int u = 0; u < U; ++u) derive_v2<C, CH, (ISI != 0)>(dref[u], st[u]);
         }
@@ -210,11 +176,11 @@ __global__ __launch_bounds__(256, (pix_min_waves<U>())) void series_pixels_kerne
                 if constexpr (PF) {
                     frame_pix<C, CH, U, PF, ISI>(a.thr, st, buf[j], buf[(j + 1) & 3], acc);
                     __builtin_amdgcn_sched_barrier(0);
-                    load_frame(tf + 3, buf[j]);
+                    ld.frame(tf + 3, buf[j]);
                 } else {
                     frame_pix<C, CH, U, PF, ISI>(a.thr, st, rb, buf[j], acc);
                     __builtin_amdgcn_sched_barrier(0);
-                    load_frame(tf + 4, buf[j]);
+                    ld.frame(tf + 4, buf[j]);
                 }
             }
         }
@@ -233,10 +199,10 @@ __global__ __launch_bounds__(256, (pix_min_waves<U>())) void series_pixels_kerne
         // contiguous bytes of the map
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (voff[u] == 0x80000000u) continue;
-            const uint32_t idx = v0 + (uint32_t)(u * 64) + lane;
-            const uint32_t r = idx / vpr;
-            const uint32_t x4 = (idx - r * vpr) * 4u;
+            if (voff[u] == kNoSlot) continue;
+            const dips_sched::Slot sl =
+                dips_sched::region_slot(rc, vpr, nvec, a.width, (uint32_t)C, fb, v0 + (uint32_t)(u * 64) + lane);
+            const uint32_t r = sl.r, x4 = sl.x4;
             dips_series_entry* e = a.sums + ((uint64_t)r * rc.w + x4);
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
@@ -335,20 +301,13 @@ __global__ __launch_bounds__(256) void pixels_generic_kernel(PixGenericArgs a) {
 // ---------------------------------------------------------------------------
 // Host-side launchers (instantiation table)
 // ---------------------------------------------------------------------------
-template <int C, int CH, bool PF, int ISI>
-static const void* pix_ptr() {
-    return reinterpret_cast<const void*>(&series_pixels_kernel<C, CH, kUnrollPix, PF, ISI>);
-}
-
 template <int C, int ISI>
 static const void* pick_pix(int chroma, bool pf) {
-    switch (chroma) {
-        case 0: return pf ? pix_ptr<C, 0, true, ISI>() : pix_ptr<C, 0, false, ISI>();
-        case 1: return pf ? pix_ptr<C, 1, true, ISI>() : pix_ptr<C, 1, false, ISI>();
-        case 2: return pf ? pix_ptr<C, 2, true, ISI>() : pix_ptr<C, 2, false, ISI>();
-        case 3: return pf ? pix_ptr<C, 3, true, ISI>() : pix_ptr<C, 3, false, ISI>();
-        default: return nullptr;
-    }
+    return dispatch_chroma(chroma, [&](auto ch) {
+        return dispatch_flag(pf, [&](auto p) {
+            return reinterpret_cast<const void*>(&series_pixels_kernel<C, ch.value, kUnrollPix, p.value, ISI>);
+        });
+    });
 }
 
 const void* series_pixels_kernel_ptr(int channels, int chroma, bool per_frame, int isi) {

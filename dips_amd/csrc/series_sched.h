@@ -9,6 +9,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "series_slots.h"
+
 namespace dips_sched {
 
 // The schedule of one fast launch.  ok false: the generic kernel runs.
@@ -415,8 +417,9 @@ Geom background_geometry(uint64_t frame_bytes, uint32_t n_frames, int unroll, ui
     return q;
 }
 
-// The vecs (4 pixels) a fast regional kernel leaves out: those that would
-// read past the frame's end, i.e. that start within 3 pixels of it.  Vecs of
+// The vecs (4 pixels) a fast regional kernel leaves out: those that
+// vec_crosses_frame_end (series_slots.h, the kernels' own test) finds to read
+// past the frame's end, i.e. that start within 3 pixels of it.  Vecs of
 // a row are 4 pixels apart and a full vec ends inside its row, so that is at
 // most the partial last vec of each of the region's last rows: one row for
 // frames 3 or more pixels wide, up to 4 for narrower ones.  row(r, i0) is
@@ -431,9 +434,43 @@ auto for_frame_end_tail_rows(uint32_t width, uint32_t height, uint32_t roi_x, ui
     const uint32_t i0 = (roi_w - 1u) & ~3u;  // the last vec of a region row
     const uint64_t npx = (uint64_t)width * height;
     for (uint32_t r = roi_h; r-- > 0 && roi_h - r <= 4u;) {
-        if ((uint64_t)(roi_y + r) * width + roi_x + i0 + 4u <= npx) break;  // it and every earlier row fit
+        // in pixels: it and every earlier row fit
+        if (!vec_crosses_frame_end<uint64_t>((uint64_t)(roi_y + r) * width + roi_x + i0, 4u, npx)) break;
         const T st = row(r, i0);
         if (st != T{}) return st;
+    }
+    return T{};
+}
+
+// The same for a rows x cols grid of cells over the region {x, y, w, h}
+// (series_grid.hip: every cell is a region of its own): the partial last vec
+// of a cell row that crosses the frame's end.  These lie in the frame's last
+// row, and in frames narrower than 3 pixels in up to three rows before it;
+// cell edges grow with the column, so at most three cells of a row qualify.
+// cell_rect(row, col) gives a cell's rectangle {x, y, w, h}; tail(row, col,
+// x0, y, n) is called for the n <= 3 pixels from frame column x0 of frame row
+// y that cell (row, col) leaves out; a status other than T{} ends the walk.
+template <typename CellRect, typename Tail>
+auto for_grid_frame_end_tails(uint32_t width, uint32_t height, uint32_t y0, uint32_t h, uint32_t rows, uint32_t cols,
+                              CellRect&& cell_rect, Tail&& tail) -> decltype(tail(0u, 0u, 0u, 0u, 0u)) {
+    using T = decltype(tail(0u, 0u, 0u, 0u, 0u));
+    const uint64_t npx = (uint64_t)width * height;
+    // crosses(y, x): a vec that started at frame pixel (x, y) would cross the
+    // frame's end.  Asked of the last pixel of a row or of a cell it is a
+    // bound, not a real vec: no vec of that row / cell starts later
+    auto crosses = [&](uint64_t y, uint64_t x) { return vec_crosses_frame_end<uint64_t>(y * width + x, 4u, npx); };
+    uint32_t crow = rows - 1u;  // the grid row of frame row y
+    for (uint32_t y = y0 + h; y-- > y0;) {
+        if (!crosses(y, (uint64_t)width - 1u)) break;  // every vec of this and the earlier rows fits
+        while (cell_rect(crow, 0u).y > y) --crow;
+        for (uint32_t c = cols; c-- > 0;) {
+            const auto rc = cell_rect(crow, c);
+            if (!crosses(y, (uint64_t)rc.x + rc.w - 1u)) break;  // so does every vec of the earlier columns
+            const uint32_t x0 = rc.x + ((rc.w - 1u) & ~3u);      // the cell row's last vec
+            if (rc.w % 4u == 0u || !crosses(y, x0)) continue;
+            const T st = tail(crow, c, x0, y, rc.x + rc.w - x0);
+            if (st != T{}) return st;
+        }
     }
     return T{};
 }

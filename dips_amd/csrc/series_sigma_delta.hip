@@ -17,13 +17,11 @@
 // accumulating call promises that the held state is in range
 // (include/dips_hip.h).
 //
-// The fast kernel takes series_background_kernel's skeleton
-// (series_background.hip): rows padded to 8 vecs per mask word, a tile = 64 *
-// U flat vecs, per-slot offsets once per tile, raw buffer loads through a
-// wave-uniform descriptor, the 4-slot frame ring, one part always (the
-// recurrence is sequential in t, tiles are the only parallelism), the DPP OR
-// and one store per word, the state read (accumulate) and written once per
-// call and plane through the plane's own descriptor.  The body differs:
+// The fast kernel has series_background_kernel's shape (the regional
+// skeleton, series_region.h): word-padded slots with state, one part always
+// (the recurrence is sequential in t, tiles are the only parallelism), the
+// state read (accumulate) and written once per call and plane through the
+// plane's own descriptor.  The body differs:
 //
 //   M and V of a vec are 4 VGPRs, packed i16 pairs in pair_planes<C>'s pixel
 //   order (pixels (0, 1) and (2, 3)).  J is a packed max / min over the u16
@@ -39,7 +37,7 @@
 // (run_sigma_delta_device); the two launches write disjoint addresses.
 #include <algorithm>
 
-#include "series_common.h"
+#include "series_region.h"
 #include "series_sigma_delta.h"
 
 namespace dips {
@@ -110,11 +108,7 @@ __device__ __forceinline__ void frame_sigma_delta(const SdRate& q, i16x2 (&m)[U]
             nib |= ((neg >> 15) & 1u) << (2 * k);
             nib |= (neg >> 31) << (2 * k + 1);
         }
-        uint32_t w = (nib << sh) & nm[u];
-        w |= DIPS_DPP(w, 0xB1);   // quad_perm [1,0,3,2]  (xor 1)
-        w |= DIPS_DPP(w, 0x4E);   // quad_perm [2,3,0,1]  (xor 2)
-        w |= DIPS_DPP(w, 0x141);  // row_half_mirror      (xor 7 inside 8 lanes)
-        word[u] = w;
+        word[u] = nibble_word(nib, sh, nm[u]);
     }
 }
 
@@ -123,8 +117,6 @@ __device__ __forceinline__ void frame_sigma_delta(const SdRate& q, i16x2 (&m)[U]
 #ifndef DIPS_SD_WAVES
 #define DIPS_SD_WAVES 4
 #endif
-
-constexpr uint32_t kSdNone = 0x80000000u;  // an offset past every descriptor: loads give 0, stores are dropped
 
 template <int C, int CH, int U>
 __global__ __launch_bounds__(256, DIPS_SD_WAVES) void series_sigma_delta_kernel(SdArgs a) {
@@ -150,32 +142,22 @@ __global__ __launch_bounds__(256, DIPS_SD_WAVES) void series_sigma_delta_kernel(
     for (uint32_t tile = wave; tile < a.n_tiles; tile += a.n_waves) {
         const uint32_t v0 = tile * (uint32_t)(64 * U);
 
-        // per lane-slot, once per tile: the byte offset into a frame (kSdNone
-        // for a slot beyond the region's right edge or rows and for the vec
-        // that would cross the frame's end), the valid pixels of its nibble,
-        // the byte offset of its pixels in a state plane with their count
-        // (0: a slot that holds no state), and for the first lane of a group
-        // the byte offset of the group's word -- kSdNone when there is no
-        // mask or the word holds a vec that was left out
+        // per lane-slot, once per tile: where it loads from, the valid pixels
+        // of its nibble, the byte offset of its pixels in a state plane with
+        // their count (0: none), and for the first lane of a group the byte
+        // offset of the group's word -- kNoSlot when there is no mask or the
+        // word holds a vec that was left out
         uint32_t voff[U], nm[U], woff[U], soff[U], spx[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t idx = v0 + (uint32_t)(u * 64) + lane;
-            const uint32_t r = idx / vpr8;
-            const uint32_t x4 = (idx - r * vpr8) * 4u;
-            const bool in = idx < nvec8 && x4 < rc.w;
-            const uint32_t off = in ? ((rc.y + r) * a.width + rc.x + x4) * (uint32_t)C : 0u;
-            const bool ok = in && off + (uint32_t)F::VB <= fb;
-            voff[u] = ok ? off : kSdNone;
-            const uint32_t left = in ? min(4u, rc.w - x4) : 0u;
-            nm[u] = ((1u << left) - 1u) << sh;
-            spx[u] = ok ? left : 0u;
-            soff[u] = ok ? (r * rc.w + x4) * 2u : kSdNone;
-            uint32_t out = (in && !ok) ? 1u : 0u;
-            out |= DIPS_DPP(out, 0xB1);
-            out |= DIPS_DPP(out, 0x4E);
-            out |= DIPS_DPP(out, 0x141);
-            woff[u] = ((lane & 7u) == 0u && idx < nvec8 && out == 0u && a.mask != nullptr) ? (idx >> 3) * 4u : kSdNone;
+            const dips_sched::WordSlot s = dips_sched::region_word_slot(rc, vpr8, nvec8, a.width, (uint32_t)C, fb, idx);
+            voff[u] = s.voff;
+            nm[u] = dips_sched::slot_word_bits(s.left, sh);
+            spx[u] = s.ok ? s.left : 0u;
+            soff[u] = s.ok ? (s.r * rc.w + s.x4) * 2u : kNoSlot;
+            const uint32_t out = group8_or((s.in && !s.ok) ? 1u : 0u);  // by all lanes: no branch around it
+            woff[u] = ((lane & 7u) == 0u && idx < nvec8 && out == 0u && a.mask != nullptr) ? (idx >> 3) * 4u : kNoSlot;
         }
 
         auto load_at = [&](const uint8_t* p, uint32_t (&dst)[U][NDW]) {
@@ -192,7 +174,7 @@ __global__ __launch_bounds__(256, DIPS_SD_WAVES) void series_sigma_delta_kernel(
             const __amdgpu_buffer_rsrc_t r = make_rsrc(a.mask + (uint64_t)tf * mfb, a.mask != nullptr ? mfb : 0u);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (woff[u] != kSdNone) __builtin_amdgcn_raw_buffer_store_b32(word[u], r, woff[u], 0, 0);
+                if (woff[u] != kNoSlot) __builtin_amdgcn_raw_buffer_store_b32(word[u], r, woff[u], 0, 0);
             }
         };
         // plane p of the state alone: soff + 8 <= plane_bytes for a whole
@@ -202,17 +184,8 @@ __global__ __launch_bounds__(256, DIPS_SD_WAVES) void series_sigma_delta_kernel(
                 make_rsrc(reinterpret_cast<const uint8_t*>(a.state) + (uint64_t)p * plane_bytes, plane_bytes);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                uint32_t lo = 0u, hi = 0u;
-                if (spx[u] == 4u) {
-                    const auto x = __builtin_amdgcn_raw_buffer_load_b64(r, soff[u], 0, 0);
-                    lo = x[0];
-                    hi = x[1];
-                } else {
-                    if (spx[u] > 0u) lo = (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, soff[u], 0, 0);
-                    if (spx[u] > 1u)
-                        lo |= (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, soff[u] + 2u, 0, 0) << 16;
-                    if (spx[u] > 2u) hi = (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, soff[u] + 4u, 0, 0);
-                }
+                uint32_t lo, hi;
+                load_state(r, soff[u], spx[u], lo, hi);
                 dst[u][0] = as_i16x2(lo);
                 dst[u][1] = as_i16x2(hi);
             }
@@ -367,21 +340,13 @@ __global__ __launch_bounds__(256) void sigma_delta_generic_kernel(SdGenericArgs 
 // ---------------------------------------------------------------------------
 // Host-side launchers (instantiation table)
 // ---------------------------------------------------------------------------
-template <int C, int CH>
-static const void* sigma_delta_ptr(bool small) {
-    return small ? reinterpret_cast<const void*>(&series_sigma_delta_kernel<C, CH, 1>)
-                 : reinterpret_cast<const void*>(&series_sigma_delta_kernel<C, CH, kUnrollSigmaDelta>);
-}
-
 template <int C>
 static const void* pick_sigma_delta(int chroma, bool small) {
-    switch (chroma) {
-        case 0: return sigma_delta_ptr<C, 0>(small);
-        case 1: return sigma_delta_ptr<C, 1>(small);
-        case 2: return sigma_delta_ptr<C, 2>(small);
-        case 3: return sigma_delta_ptr<C, 3>(small);
-        default: return nullptr;
-    }
+    return dispatch_chroma(chroma, [&](auto ch) {
+        return dispatch_flag(small, [&](auto sm) {
+            return reinterpret_cast<const void*>(&series_sigma_delta_kernel<C, ch.value, sm.value ? 1 : kUnrollSigmaDelta>);
+        });
+    });
 }
 
 const void* series_sigma_delta_kernel_ptr(int channels, int chroma, bool small_tile) {

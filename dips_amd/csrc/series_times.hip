@@ -14,16 +14,14 @@
 // The fast kernel takes series_mask_kernel's per-frame step (derive_v2, the
 // subtract and the strict compare in the 2^22-scaled domain; one intensity
 // form serves every tau, so there is no integer-sum axis) and
-// series_pixels_kernel's ownership and output: a persistent grid over items
-// (frame part, tile), a tile = 64 * U vecs of 4 horizontally consecutive
-// pixels of one region row flattened over the region, per-slot byte offsets
-// once per tile, raw buffer loads through a wave-uniform descriptor over the
-// whole frame, the 4-slot frame ring, and the state of a lane's pixels in
+// series_pixels_kernel's ownership and output: the regional skeleton
+// (series_region.h) over the flat slots of the region (series_slots.h
+// region_slot) with the frames-only ring, and the state of a lane's pixels in
 // registers across the frames of the item, stored by that lane with plain
 // stores.  The pixels of a partial vec beyond the region's right edge are
 // computed from the bytes that follow and never stored; a partial vec that
 // would read past the frame's end is left out (its <= 3 pixels go to the
-// generic kernel; run_times_device applies the same test).
+// generic kernel: run_times_device, by for_frame_end_tail_rows).
 //
 // One part (MP = false): a wave owns every frame of its pixels.  It starts
 // from the initial state, or when the call accumulates from the state the
@@ -44,7 +42,7 @@
 // with len the part's frame count, known from the geometry.  In per-frame
 // mode a part's first reference is the frame before it, so a part's bits are
 // those of the whole clip and the result does not depend on the part count.
-#include "series_v2_frame.h"
+#include "series_region.h"
 
 namespace dips {
 
@@ -110,43 +108,25 @@ __global__ __launch_bounds__(256, DIPS_TIMES_WAVES) void series_times_kernel(Tim
     const uint32_t nvec = vpr * rc.h;
     const uint64_t npx = (uint64_t)rc.w * rc.h;  // u32 per plane
 
-    const uint32_t plen = a.part_frames;
-    const uint64_t pitems = (uint64_t)((a.n_frames + plen - 1) / plen) * a.n_tiles;
+    const uint64_t pitems = region_items(a.n_frames, a.part_frames, a.n_tiles);
     for (uint64_t it = wave; it < pitems; it += a.n_waves) {
-        const uint32_t part = (uint32_t)(it / a.n_tiles);
-        const uint32_t tile = (uint32_t)(it - (uint64_t)part * a.n_tiles);
-        const uint32_t v0 = tile * (uint32_t)(64 * U);
-        const uint32_t t0 = part * plen;
-        const uint32_t tend = min(a.n_frames, t0 + plen);
-        const uint32_t n = tend - t0;  // frames of this item (>= 1)
-        const uint32_t tlast = tend - 1;
+        const RegionItem i = region_item(it, a.n_frames, a.part_frames, a.n_tiles);
+        const uint32_t part = i.part, t0 = i.t0, n = i.n, tlast = i.tlast;
+        const uint32_t v0 = i.tile * (uint32_t)(64 * U);
 
-        // per lane-slot, once per tile: the byte offset into a frame (past
-        // the descriptor for a slot beyond the region or the one vec that
-        // would cross the frame's end: its loads return zeros), the index of
+        // per lane-slot, once per tile: where it loads from, the index of
         // its first pixel in a plane and how many of its pixels are stored
-        // (0 for such a slot)
         uint32_t voff[U], pbase[U], left[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const uint32_t idx = v0 + (uint32_t)(u * 64) + lane;
-            const uint32_t r = idx / vpr;
-            const uint32_t x4 = (idx - r * vpr) * 4u;
-            const uint32_t off = ((rc.y + r) * a.width + rc.x + x4) * (uint32_t)C;
-            const bool ok = idx < nvec && off + (uint32_t)F::VB <= fb;
-            voff[u] = ok ? off : 0x80000000u;
-            pbase[u] = ok ? r * rc.w + x4 : 0u;
-            left[u] = ok ? min(4u, rc.w - x4) : 0u;
+            const dips_sched::Slot s =
+                dips_sched::region_slot(rc, vpr, nvec, a.width, (uint32_t)C, fb, v0 + (uint32_t)(u * 64) + lane);
+            voff[u] = s.voff;
+            pbase[u] = s.ok ? s.r * rc.w + s.x4 : 0u;
+            left[u] = s.ok ? dips_sched::vec_px_inside(rc.w, s.x4) : 0u;
         }
 
-        auto load_at = [&](const uint8_t* p, uint32_t (&dst)[U][NDW]) {
-            const __amdgpu_buffer_rsrc_t r = make_rsrc(p, fb);
-#pragma unroll
-            for (int u = 0; u < U; ++u) load_vec<C, kAuxNT>(r, voff[u], dst[u]);
-        };
-        auto load_frame = [&](uint32_t tf, uint32_t (&dst)[U][NDW]) {
-            load_at(a.frames + (uint64_t)min(tf, tlast) * fb, dst);
-        };
+        const FrameLoader<C, U> ld{a.frames, fb, tlast, voff};
 
         // ring: frame k of the item in slot k & 3; the reference (the frame
         // before the part in per-frame mode) only leaves its state
@@ -156,11 +136,8 @@ __global__ __launch_bounds__(256, DIPS_TIMES_WAVES) void series_times_kernel(Tim
         {
             const uint8_t* rp = PF ? (t0 == 0 ? a.ref0 : a.frames + (uint64_t)(t0 - 1) * fb) : a.ref0;
             uint32_t rb[U][NDW];
-            load_at(rp, rb);
-            load_frame(t0, buf[0]);
-            load_frame(t0 + 1, buf[1]);
-            load_frame(t0 + 2, buf[2]);
-            load_frame(t0 + 3, buf[3]);
+            ld.at(rp, rb);
+            ld.fill(t0, buf);
             // the state the fold starts from, while the frames are in flight
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -198,7 +175,7 @@ __global__ __launch_bounds__(256, DIPS_TIMES_WAVES) void series_times_kernel(Tim
                 const uint32_t kj = k + (uint32_t)j;
                 frame_times<C, CH, U, PF, MP>(a.thr, g0 + kj, kj + 1u, st, buf[j], acc);
                 __builtin_amdgcn_sched_barrier(0);
-                load_frame(t0 + kj + 4u, buf[j]);
+                ld.frame(t0 + kj + 4u, buf[j]);
             }
         }
         // tail: up to 3 frames, already in flight in their slots
@@ -243,7 +220,7 @@ __global__ __launch_bounds__(256) void times_combine_kernel(TimesCombineArgs a) 
     const uint32_t j = (uint32_t)(q / a.roi.w);
     const uint32_t i = (uint32_t)(q - (uint64_t)j * a.roi.w);
     const uint32_t off = ((a.roi.y + j) * a.width + a.roi.x + (i & ~3u)) * a.channels;
-    if (off + 4u * a.channels > a.frame_bytes) return;
+    if (dips_sched::vec_crosses_frame_end(off, 4u * a.channels, a.frame_bytes)) return;
     uint32_t first = kTimeNone, last = kTimeNone, rmax = 0u, rcur = 0u;
     if (a.accumulate != 0u) {
         first = a.times[q];
@@ -281,13 +258,7 @@ __global__ __launch_bounds__(256) void times_generic_kernel(TimesGenericArgs a) 
     const uint32_t py = a.rect.y + (uint32_t)(q / a.rect.w);
     const uint32_t px = a.rect.x + (uint32_t)(q % a.rect.w);
     const uint64_t pb = ((uint64_t)py * a.width + px) * (uint64_t)C;
-    auto load_px = [&](const uint8_t* base) -> float {
-        uint32_t v[3] = {0u, 0u, 0u};
-#pragma unroll
-        for (int c = 0; c < (C < 3 ? C : 3); ++c) v[c] = base[pb + c];
-        if constexpr (C == 1) v[1] = v[2] = v[0];
-        return intensity_rgb(v[0], v[1], v[2], a.chroma);
-    };
+    auto load_px = [&](const uint8_t* base) -> float { return generic_intensity<C>(base, pb, a.chroma); };
     const uint64_t npx = (uint64_t)a.roi.w * a.roi.h;
     uint32_t* e = a.times + ((uint64_t)(py - a.roi.y) * a.roi.w + (px - a.roi.x));
     uint32_t first = kTimeNone, last = kTimeNone, rmax = 0u, rcur = 0u;
@@ -320,21 +291,15 @@ __global__ __launch_bounds__(256) void times_generic_kernel(TimesGenericArgs a) 
 // ---------------------------------------------------------------------------
 // Host-side launchers (instantiation table)
 // ---------------------------------------------------------------------------
-template <int C, int CH, bool PF>
-static const void* times_ptr(bool mp) {
-    return mp ? reinterpret_cast<const void*>(&series_times_kernel<C, CH, kUnrollTimes, PF, true>)
-              : reinterpret_cast<const void*>(&series_times_kernel<C, CH, kUnrollTimes, PF, false>);
-}
-
 template <int C>
 static const void* pick_times(int chroma, bool pf, bool mp) {
-    switch (chroma) {
-        case 0: return pf ? times_ptr<C, 0, true>(mp) : times_ptr<C, 0, false>(mp);
-        case 1: return pf ? times_ptr<C, 1, true>(mp) : times_ptr<C, 1, false>(mp);
-        case 2: return pf ? times_ptr<C, 2, true>(mp) : times_ptr<C, 2, false>(mp);
-        case 3: return pf ? times_ptr<C, 3, true>(mp) : times_ptr<C, 3, false>(mp);
-        default: return nullptr;
-    }
+    return dispatch_chroma(chroma, [&](auto ch) {
+        return dispatch_flag(pf, [&](auto p) {
+            return dispatch_flag(mp, [&](auto m) {
+                return reinterpret_cast<const void*>(&series_times_kernel<C, ch.value, kUnrollTimes, p.value, m.value>);
+            });
+        });
+    });
 }
 
 const void* series_times_kernel_ptr(int channels, int chroma, bool per_frame, bool parts) {
