@@ -52,6 +52,8 @@ MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # DIPS_MORPH_ER
 MORPH_BOX, MORPH_DIAMOND = 0, 1  # DIPS_MORPH_BOX, DIPS_MORPH_DIAMOND
 MORPH_MAX_RADIUS = 15  # DIPS_MORPH_MAX_RADIUS
 VOTE_MAX_WINDOW = 31  # DIPS_VOTE_MAX_WINDOW
+SELECT_CLEAR_BORDER, SELECT_DROPPED = 0x1, 0x2  # DIPS_SELECT_CLEAR_BORDER, DIPS_SELECT_DROPPED
+LOGIC_AND, LOGIC_OR, LOGIC_XOR, LOGIC_ANDNOT, LOGIC_NOT = 0, 1, 2, 3, 4  # DIPS_LOGIC_AND .. DIPS_LOGIC_NOT
 BG_SELECTIVE = 1  # DIPS_BG_SELECTIVE
 BG_MAX_RATE_SHIFT = 8  # DIPS_BG_MAX_RATE_SHIFT
 SD_MAX_AMP = 15  # DIPS_SD_MAX_AMP
@@ -206,6 +208,8 @@ def load() -> ctypes.CDLL:
             "dips_mask_tracks": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, _vp, _vp, _vp, _vp], st),
             "dips_mask_morph": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p], st),
             "dips_mask_vote": ([_vp, _u8p, u32, u32, u32, u32, u32, _u8p, _u8p, _u8p], st),
+            "dips_mask_select": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, u32, u32, _u8p, _vp], st),
+            "dips_mask_logic": ([_vp, _u8p, u32, u32, u32, u32, _u8p, u32, _u8p], st),
             "dips_mask_counts": ([_vp, _u8p, u32, u32, u32, u32, u32, _vp], st),
             "dips_mask_pixel_times": ([_vp, _u8p, u32, u32, u32, u32, u32, _vp, _vp], st),
             "dips_series_si": ([P(SeriesEntry)], ctypes.c_double),

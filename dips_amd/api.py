@@ -62,6 +62,15 @@ class MorphShape(enum.IntEnum):
     Diamond = _lib.MORPH_DIAMOND  # |dx| + |dy| <= rx (ry == rx)
 
 
+class MaskLogic(enum.IntEnum):
+    """The operation of dips_mask_logic."""
+    And = _lib.LOGIC_AND
+    Or = _lib.LOGIC_OR
+    Xor = _lib.LOGIC_XOR
+    AndNot = _lib.LOGIC_ANDNOT  # a & ~b
+    Not = _lib.LOGIC_NOT        # ~a inside the region; takes no b
+
+
 class VideoPathNotSpecifiedError(Exception):
     """dips/src/lib.rs:173-186"""
 
@@ -783,6 +792,49 @@ def _vote_option(vote) -> Tuple[int, int]:
     return _vote_args(vote)
 
 
+def _select_args(connectivity, min_area, max_area, clear_border, dropped, chunk_frames) -> Tuple[int, int, int, int, int]:
+    """(connectivity, min_area, max_area, select bits, chunk_frames) of
+    dips_mask_select, checked."""
+    if int(connectivity) not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    for name, v in (("min_area", min_area), ("max_area", max_area), ("chunk_frames", chunk_frames)):
+        if int(v) < 0 or int(v) > 0xFFFFFFFF:
+            raise ValueError(f"{name} must be a non-negative 32-bit integer")
+    if int(max_area) != 0 and int(max_area) < int(min_area):
+        raise ValueError("max_area must be 0 (no upper bound) or at least min_area")
+    bits = (_lib.SELECT_CLEAR_BORDER if clear_border else 0) | (_lib.SELECT_DROPPED if dropped else 0)
+    return int(connectivity), int(min_area), int(max_area), bits, int(chunk_frames)
+
+
+_SELECT_KEYS = ("min_area", "max_area", "clear_border", "connectivity", "fill_holes")
+
+
+def _select_option(select) -> dict:
+    """change_boxes' select: a dict with keys from min_area, max_area,
+    clear_border, connectivity and fill_holes (False, True or the largest
+    hole to fill), checked; the defaults select nothing away."""
+    if not isinstance(select, dict) or any(k not in _SELECT_KEYS for k in select):
+        raise ValueError("select must be a dict with keys from " + ", ".join(_SELECT_KEYS))
+    opt = {"min_area": 1, "max_area": 0, "clear_border": False, "connectivity": 8, "fill_holes": False}
+    opt.update(select)
+    _select_args(opt["connectivity"], opt["min_area"], opt["max_area"], opt["clear_border"], False, 0)
+    fill = opt["fill_holes"]
+    if not isinstance(fill, bool) and (int(fill) < 0 or int(fill) > 0xFFFFFFFF):
+        raise ValueError("fill_holes must be False, True or a non-negative 32-bit integer")
+    return opt
+
+
+def _logic_op(op, has_b: bool) -> int:
+    """The op of dips_mask_logic, checked against whether b is given."""
+    try:
+        op = int(MaskLogic(op))
+    except ValueError:
+        raise ValueError("op must be a MaskLogic (0 .. 4)") from None
+    if (op == MaskLogic.Not) == has_b:
+        raise ValueError("MaskLogic.Not takes no b, every other op needs one")
+    return op
+
+
 def _mask_host_args(mask) -> Tuple[np.ndarray, int, int, int]:
     """(bits, region width, region height, n) of a host ChangeMask, checked
     as the mask statistics take it."""
@@ -826,6 +878,27 @@ def _mask_device_outputs(mask, outs) -> None:
         for b0, b1 in spans[i + 1:]:
             if a0 < b1 and b0 < a1:
                 raise ValueError("an output must not overlap the mask or the other output")
+
+
+def _mask_device_tensors(ins, outs) -> None:
+    """The device tensors of a mask-to-mask call: contiguous HIP tensors,
+    4-byte aligned, no output sharing a byte with an input or another output
+    (the inputs may share theirs)."""
+    for t in list(ins) + list(outs):
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("device path needs contiguous HIP tensors")
+        if t.numel() and (t.data_ptr() & 3) != 0:
+            raise ValueError("the tensors must be 4-byte aligned")
+
+    def span(t):
+        return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+
+    outs = [t for t in outs if t.numel()]
+    for i, o in enumerate(outs):
+        for other in [t for t in ins if t.numel()] + outs[i + 1:]:
+            (a0, a1), (b0, b1) = span(o), span(other)
+            if a0 < b1 and b0 < a1:
+                raise ValueError("an output must not overlap an input or the other output")
 
 
 def _mask_grid_args(rows, cols, rw: int, rh: int, n: int) -> Tuple[int, int]:
@@ -903,10 +976,17 @@ class DiffSeriesOperator:
         self._dev = _Handle(_params(fmt=self.fmt, mode=self.mode, tau=tau,
                                     chroma_filter=chroma_filter,
                                     flags=flags | _lib.FLAG_DEVICE_PTRS), device)
+        # hysteresis_mask's device handles at a higher tau, by that tau
+        self._strong = {}
+        self._strong_params = dict(fmt=self.fmt, mode=self.mode, chroma_filter=chroma_filter,
+                                   flags=flags | _lib.FLAG_DEVICE_PTRS)
 
     def close(self) -> None:
         self._host.close()
         self._dev.close()
+        for hd in self._strong.values():
+            hd.close()
+        self._strong = {}
 
     # -- host arrays -------------------------------------------------------
     def __call__(self, frames: np.ndarray, ref: Optional[np.ndarray] = None,
@@ -1092,10 +1172,11 @@ class DiffSeriesOperator:
             out.ctypes.data if out.size else None))
         return ChangeMask(out, rw)
 
-    def run_change_mask_device(self, frames, mask_out, roi=None, ref=None, stream=None) -> None:
+    def run_change_mask_device(self, frames, mask_out, roi=None, ref=None, stream=None, _handle=None) -> None:
         """Asynchronous: frames / ref uint8 device tensors, mask_out a uint8
         device tensor of shape [N, h, row_bytes] of the region (4-byte
         aligned), every byte of which is written."""
+        hd = self._dev if _handle is None else _handle
         n, h, w = _frame_geometry(frames, self.fmt)
         rh, rw = self._region(roi, h, w)
         if tuple(mask_out.shape) != (n, rh, 4 * ((rw + 31) // 32)):
@@ -1109,10 +1190,10 @@ class DiffSeriesOperator:
                 raise ValueError("frames, ref and mask_out must be uint8 tensors")
         if ref is not None and ref.numel() != h * w * int(self.fmt):
             raise ValueError("ref must have the size of one frame")
-        lib = self._dev._lib
-        with _stream_of(self._dev, frames, stream):
-            self._dev.check(lib.dips_diff_change_mask(
-                self._dev.ptr, w, h, frames.data_ptr() if n else None, n,
+        lib = hd._lib
+        with _stream_of(hd, frames, stream):
+            hd.check(lib.dips_diff_change_mask(
+                hd.ptr, w, h, frames.data_ptr() if n else None, n,
                 ref.data_ptr() if ref is not None else None, _roi_arg(roi),
                 mask_out.data_ptr() if mask_out.numel() else None))
 
@@ -1545,6 +1626,175 @@ class DiffSeriesOperator:
                 history_out.data_ptr() if history_out is not None else None,
                 out.data_ptr() if n else None))
 
+    # -- the selection of components and the logic of masks (dips_mask_select,
+    # -- dips_mask_logic) ------------------------------------------------------
+    def mask_select(self, mask: ChangeMask, marker: Optional[ChangeMask] = None, connectivity: int = 8,
+                    min_area: int = 1, max_area: int = 0, clear_border: bool = False, dropped: bool = False,
+                    chunk_frames: int = 0) -> Tuple[ChangeMask, np.ndarray]:
+        """(selected, counts): of every frame of `mask` the union of the
+        components (mask_components' under `connectivity`) that have at
+        least min_area and, unless max_area is 0, at most max_area pixels,
+        that hold a set bit of `marker` (None: no such condition; a marker
+        of one frame serves every frame) and, with clear_border, that have
+        no pixel on the region's border; dropped=True gives the mask minus
+        that union.  counts uint32 [n]: the kept components per frame.  A
+        mask that lives on the device goes through run_mask_select_device."""
+        bits, rw, rh, n = _mask_host_args(mask)
+        conn, lo, hi, sel, chunk = _select_args(connectivity, min_area, max_area, clear_border, dropped, chunk_frames)
+        mk, mk_n = None, 0
+        if marker is not None:
+            mk, mw, mh, mk_n = _mask_host_args(marker)
+            if (mw, mh) != (rw, rh) or mk_n not in (1, n):
+                raise ValueError("marker must hold one frame or the mask's frames of the mask's region")
+        out = np.zeros_like(bits)
+        counts = np.zeros(n, dtype=np.uint32)
+        self._host.check(self._host._lib.dips_mask_select(
+            self._host.ptr, bits.ctypes.data if n else None, n, rw, rh, conn, lo, hi, sel,
+            mk.ctypes.data if mk is not None and n else None, mk_n if n else 0, chunk,
+            out.ctypes.data if n else None, counts.ctypes.data if n else None))
+        return ChangeMask(out, rw), counts
+
+    def run_mask_select_device(self, mask, width: int, out, marker=None, counts_out=None, connectivity: int = 8,
+                               min_area: int = 1, max_area: int = 0, clear_border: bool = False,
+                               dropped: bool = False, chunk_frames: int = 0, stream=None) -> None:
+        """Asynchronous: mask and out uint8 device tensors [N, h, row_bytes]
+        as run_change_mask_device writes them for a region `width` pixels
+        wide, marker (None: none) such a tensor of 1 or N frames, counts_out
+        (None: not produced) a 4-byte device tensor [N]; all 4-byte aligned,
+        no output overlapping an input or the other output.  Every byte of
+        out and every entry of counts_out is written."""
+        rw, rh, n = _mask_device_args(mask, width)
+        conn, lo, hi, sel, chunk = _select_args(connectivity, min_area, max_area, clear_border, dropped, chunk_frames)
+        if tuple(out.shape) != tuple(mask.shape) or out.dtype != mask.dtype:
+            raise ValueError("out must be a uint8 tensor of the shape of mask")
+        mk_n = 0
+        if marker is not None:
+            mw, mh, mk_n = _mask_device_args(marker, width)
+            if mh != rh or mk_n not in (1, n):
+                raise ValueError("marker must hold one frame or the mask's frames of the mask's region")
+        if counts_out is not None and (tuple(counts_out.shape) != (n,) or counts_out.element_size() != 4):
+            raise ValueError("counts_out must be a 4-byte tensor of shape [N]")
+        ins = [mask] + ([marker] if marker is not None else [])
+        outs = [out] + ([counts_out] if counts_out is not None else [])
+        _mask_device_tensors(ins, outs)
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_select(
+                self._dev.ptr, mask.data_ptr() if n else None, n, rw, rh, conn, lo, hi, sel,
+                marker.data_ptr() if marker is not None and n else None, mk_n if n else 0, chunk,
+                out.data_ptr() if n else None, counts_out.data_ptr() if counts_out is not None and n else None))
+
+    def mask_logic(self, a: ChangeMask, op, b: Optional[ChangeMask] = None) -> ChangeMask:
+        """`a` op `b` bit by bit inside the region (MaskLogic: And, Or, Xor,
+        AndNot = a & ~b, Not = ~a with no b); a `b` of one frame, a static
+        zone mask, serves every frame of `a`.  Masks that live on the device
+        go through run_mask_logic_device."""
+        op = _logic_op(op, b is not None)
+        bits, rw, rh, n = _mask_host_args(a)
+        bb, b_n = None, 0
+        if b is not None:
+            bb, bw, bh, b_n = _mask_host_args(b)
+            if (bw, bh) != (rw, rh) or b_n not in (1, n):
+                raise ValueError("b must hold one frame or a's frames of a's region")
+        out = np.zeros_like(bits)
+        self._host.check(self._host._lib.dips_mask_logic(
+            self._host.ptr, bits.ctypes.data if n else None, n, rw, rh, op,
+            bb.ctypes.data if bb is not None and n else None, b_n if n else 0, out.ctypes.data if n else None))
+        return ChangeMask(out, rw)
+
+    def run_mask_logic_device(self, a, width: int, out, op, b=None, stream=None) -> None:
+        """Asynchronous: a and out uint8 device tensors [N, h, row_bytes] as
+        run_change_mask_device writes them for a region `width` pixels wide,
+        b (None with MaskLogic.Not) such a tensor of 1 or N frames; all
+        4-byte aligned, out overlapping neither input.  Every byte of out is
+        written."""
+        op = _logic_op(op, b is not None)
+        rw, rh, n = _mask_device_args(a, width)
+        if tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype:
+            raise ValueError("out must be a uint8 tensor of the shape of a")
+        b_n = 0
+        if b is not None:
+            bw, bh, b_n = _mask_device_args(b, width)
+            if bh != rh or b_n not in (1, n):
+                raise ValueError("b must hold one frame or a's frames of a's region")
+        _mask_device_tensors([a] + ([b] if b is not None else []), [out])
+        lib = self._dev._lib
+        with _stream_of(self._dev, a, stream):
+            self._dev.check(lib.dips_mask_logic(
+                self._dev.ptr, a.data_ptr() if n else None, n, rw, rh, op,
+                b.data_ptr() if b is not None and n else None, b_n if n else 0, out.data_ptr() if n else None))
+
+    def mask_fill_holes(self, mask: ChangeMask, connectivity: int = 8, max_hole: int = 0) -> ChangeMask:
+        """`mask` with its holes filled.  The holes of a frame are the
+        components of its complement inside the region that do not touch the
+        region's border, taken under the dual connectivity (4 for a mask read
+        under 8, 8 for 4); with max_hole != 0 only holes of at most max_hole
+        pixels are filled.  The mask goes to the device once
+        (run_mask_fill_holes_device)."""
+        import torch
+        bits, rw, rh, n = _mask_host_args(mask)
+        if int(max_hole) < 0 or int(max_hole) > 0xFFFFFFFF:
+            raise ValueError("max_hole must be a non-negative 32-bit integer")
+        _select_args(connectivity, 1, max_hole, True, False, 0)
+        dev = torch.device("cuda", self._dev.device)
+        m = torch.from_numpy(bits).to(dev)
+        out, scratch = torch.empty_like(m), torch.empty_like(m)
+        self.run_mask_fill_holes_device(m, rw, out, scratch, connectivity, max_hole)
+        return ChangeMask(out.cpu().numpy(), rw)  # the copy waits for the stream
+
+    def run_mask_fill_holes_device(self, mask, width: int, out, scratch, connectivity: int = 8, max_hole: int = 0,
+                                   stream=None) -> None:
+        """Asynchronous mask_fill_holes: mask, out and scratch uint8 device
+        tensors of one shape [N, h, row_bytes], none overlapping another.
+        Three calls in the stream: out = NOT mask; scratch = the components
+        of out under the dual connectivity that do not touch the border (of
+        at most max_hole pixels unless 0); out = mask OR scratch."""
+        if int(max_hole) < 0 or int(max_hole) > 0xFFFFFFFF:
+            raise ValueError("max_hole must be a non-negative 32-bit integer")
+        conn, _, hole, _, _ = _select_args(connectivity, 1, max_hole, True, False, 0)
+        self.run_mask_logic_device(mask, width, out, MaskLogic.Not, stream=stream)
+        self.run_mask_select_device(out, width, scratch, connectivity=12 - conn, max_area=hole, clear_border=True,
+                                    stream=stream)
+        self.run_mask_logic_device(mask, width, out, MaskLogic.Or, scratch, stream=stream)
+
+    def hysteresis_mask(self, frames, tau_high: float, roi=None, ref=None, connectivity: int = 8) -> ChangeMask:
+        """Hysteresis thresholding: the components of the operator's change
+        mask (the weak mask, at the operator's tau) that hold a pixel of the
+        change mask at tau_high >= tau (the strong mask): whole objects from
+        the low threshold, only where the high one fires.  frames / ref:
+        numpy arrays (uploaded once) or uint8 device tensors; both masks
+        stay on the device.  The strong mask comes from a second device
+        handle at tau_high, made on first use and closed with the operator."""
+        import torch
+        tau_high = float(tau_high)
+        if not tau_high >= self.tau:
+            raise ValueError("tau_high must be at least the operator's tau")
+        if int(connectivity) not in (4, 8):
+            raise ValueError("connectivity must be 4 or 8")
+        dev = torch.device("cuda", self._dev.device)
+
+        def on_device(a):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            return torch.from_numpy(_as_u8(a)).to(dev)
+
+        frames, ref = on_device(frames), on_device(ref)
+        n, h, w = _frame_geometry(frames, self.fmt)
+        rh, rw = self._region(roi, h, w)
+        if ref is not None:
+            ref = ref.reshape(-1)
+        strong_hd = self._strong.get(tau_high)
+        if strong_hd is None:
+            strong_hd = self._strong[tau_high] = _Handle(_params(tau=tau_high, **self._strong_params),
+                                                         self._dev.device)
+        weak = torch.empty((n, rh, 4 * ((rw + 31) // 32)), dtype=torch.uint8, device=dev)
+        strong, out = torch.empty_like(weak), torch.empty_like(weak)
+        self.run_change_mask_device(frames, weak, roi=roi, ref=ref)
+        self.run_change_mask_device(frames, strong, roi=roi, ref=ref, _handle=strong_hd)
+        if n:
+            self.run_mask_select_device(weak, rw, out, marker=strong, connectivity=connectivity)
+        return ChangeMask(out.cpu().numpy(), rw)  # the copy waits for the stream
+
     # -- the statistics of a change mask (dips_mask_counts, dips_mask_pixel_times)
     def mask_counts(self, mask: ChangeMask, rows: int = 1, cols: int = 1) -> np.ndarray:
         """uint32 [n, rows, cols]: the set bits of every frame of `mask` in
@@ -1647,10 +1897,24 @@ class DiffSeriesOperator:
         kept on the device: change_boxes' mask (its roi, ref, background,
         sigma_delta, vote and morph arguments), then mask_counts on a rows x
         cols grid, mask_times from t0 = 0 and mask_sums."""
+        return self._activity(frames, roi, ref, rows, cols, morph, background, sigma_delta, vote, None)
+
+    def change_activity_selected(self, frames, select, roi=None, ref=None, rows: int = 1, cols: int = 1, morph=None,
+                                 background=None, sigma_delta=None,
+                                 vote=None) -> Tuple[np.ndarray, PixelTimes, np.ndarray]:
+        """change_activity of the mask behind change_boxes' `select` (a dict
+        with keys from min_area, max_area, clear_border, connectivity and
+        fill_holes): the statistics no longer hold the pixels of the
+        components selected away."""
+        if select is None:
+            raise ValueError("select must be a dict with keys from " + ", ".join(_SELECT_KEYS))
+        return self._activity(frames, roi, ref, rows, cols, morph, background, sigma_delta, vote, select)
+
+    def _activity(self, frames, roi, ref, rows, cols, morph, background, sigma_delta, vote, select):
         import torch
         _mask_grid_args(rows, cols, 0xFFFFFFFF, 0xFFFFFFFF, 0)  # before any device work; the region is checked below
         mask, rw, rh, n = self._change_mask_on_device(frames, roi, ref, morph, background, lambda n_: None,
-                                                      sigma_delta, vote)
+                                                      sigma_delta, vote, select)
         rows, cols = _mask_grid_args(rows, cols, rw, rh, n)
         dev = mask.device
         counts = torch.empty((n, rows, cols), dtype=torch.int32, device=dev)
@@ -1664,14 +1928,17 @@ class DiffSeriesOperator:
 
         return to_u32(counts), PixelTimes.from_array(to_u32(times)), to_u32(sums)
 
-    def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args, sigma_delta=None, vote=None):
+    def _change_mask_on_device(self, frames, roi, ref, morph, background, check_args, sigma_delta=None, vote=None,
+                               select=None):
         """(mask, region width, region height, n): the change mask of
-        change_boxes / change_tracks as a device tensor, behind its vote and
-        its morph steps; check_args(n) runs once the geometry is known."""
+        change_boxes / change_tracks as a device tensor, behind its vote,
+        its morph steps, its selection and its hole filling; check_args(n)
+        runs once the geometry is known."""
         import torch
         if sigma_delta is not None and background is not None:
             raise ValueError("sigma_delta and background exclude each other")
         sd = _sigma_delta_option(sigma_delta) if sigma_delta is not None else None
+        sel = _select_option(select) if select is not None else None
         dev = torch.device("cuda", self._dev.device)
 
         def on_device(a):
@@ -1711,11 +1978,25 @@ class DiffSeriesOperator:
             for op_, shape_, rx_, ry_ in steps:  # ping-pong: the newest mask is `mask`
                 self.run_mask_morph_device(mask, rw, other, op_, rx_, ry_, shape_)
                 mask, other = other, mask
+        if sel is not None and n:
+            if int(sel["min_area"]) > 1 or int(sel["max_area"]) != 0 or sel["clear_border"]:
+                other = torch.empty_like(mask) if other is None else other
+                self.run_mask_select_device(mask, rw, other, connectivity=sel["connectivity"],
+                                            min_area=sel["min_area"], max_area=sel["max_area"],
+                                            clear_border=sel["clear_border"])
+                mask, other = other, mask
+            fill = sel["fill_holes"]
+            if fill:  # True: every hole; a number: the holes of at most that many pixels
+                other = torch.empty_like(mask) if other is None else other
+                filled = torch.empty_like(mask)
+                self.run_mask_fill_holes_device(mask, rw, filled, other, sel["connectivity"],
+                                                0 if isinstance(fill, bool) else int(fill))
+                mask = filled
         return mask, rw, rh, n
 
     def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
                      max_boxes: int = 64, labels: bool = False, morph=None, background=None,
-                     sigma_delta=None, vote=None) -> ChangeBoxes:
+                     sigma_delta=None, vote=None, select=None) -> ChangeBoxes:
         """change_mask, then mask_components, with the mask kept on the
         device between the two: the moving objects of every frame.  frames /
         ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
@@ -1728,11 +2009,16 @@ class DiffSeriesOperator:
         per-pixel threshold (sigma_delta_mask); it excludes background.
         vote: None, or window or (window, votes) of mask_vote, applied to
         the model's mask before the morph steps with clear frames before the
-        clip (the call is one-shot: no history is carried)."""
+        clip (the call is one-shot: no history is carried).  select: None,
+        or a dict with keys from min_area, max_area, clear_border,
+        connectivity and fill_holes (True, or the largest hole to fill):
+        after the morph steps the mask becomes mask_select's of it, then
+        mask_fill_holes' of that, so that the pixels of the components
+        dropped leave the mask and not only the records."""
         import torch
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
-            lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta, vote)
+            lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta, vote, select)
         dev, k = mask.device, int(max_boxes)
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
@@ -1746,7 +2032,7 @@ class DiffSeriesOperator:
 
     def change_tracks(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
                       max_boxes: int = 64, morph=None, background=None, sigma_delta=None,
-                      vote=None) -> ChangeTracks:
+                      vote=None, select=None) -> ChangeTracks:
         """change_mask, then mask_tracks, with the mask kept on the device
         between the two: the moving objects of every frame and their
         identity from frame to frame.  The arguments are change_boxes'; the
@@ -1754,7 +2040,7 @@ class DiffSeriesOperator:
         import torch
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
-            lambda n_: _tracks_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta, vote)
+            lambda n_: _tracks_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta, vote, select)
         dev, k = mask.device, int(max_boxes)
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)

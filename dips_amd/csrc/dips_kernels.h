@@ -370,6 +370,32 @@ struct ComponentsArgs {
     uint32_t max_boxes;
 };
 
+// The selection of components of a chunk of labelled mask frames
+// (mask_select.hip), behind launch_mask_labelling on the same stream with the
+// same ComponentsArgs `cc` (its min_area is the predicate's).
+struct SelectArgs {
+    ComponentsArgs cc;
+    const uint32_t* marker;  // NULL: no marker; else frames in the mask's layout
+    uint32_t* out;           // the chunk's frames; every word is written, pad bits 0
+    uint32_t* counts;        // NULL: not produced; else the chunk's part, cleared by the host
+    uint32_t marker_stride;  // words from marker frame f to f + 1: wpf, or 0 (one frame for all)
+    uint32_t max_area;       // 0: no upper bound
+    uint32_t select;         // DIPS_SELECT_* bits
+};
+
+// Word-wise logic on mask frames (mask_select.hip): one launch, grid stride.
+struct LogicArgs {
+    const uint32_t* a;   // n_frames frames of wpf words
+    const uint32_t* b;   // b_frames frames (NULL for DIPS_LOGIC_NOT)
+    uint32_t* out;       // n_frames frames; every word is written, pad bits 0
+    uint64_t words;      // n_frames * wpf
+    uint32_t w;
+    uint32_t wpr;        // mask words per row
+    uint32_t wpf;        // mask words per frame
+    uint32_t op;         // DIPS_LOGIC_*
+    uint32_t b_bcast;    // 1: frame 0 of b serves every frame
+};
+
 // The links of a chunk of labelled mask frames to their predecessors
 // (mask_tracks.hip).  `parent` and `label` are the planes
 // launch_mask_components left, with one more plane in front: plane f + 1 is
@@ -698,6 +724,12 @@ hipError_t launch_background_generic(const BgGenericArgs& a, int channels, hipSt
 // the connected components of a chunk of mask frames (mask_components.hip):
 // every launch of the chunk, in order, on `s`
 hipError_t launch_mask_components(const ComponentsArgs& a, hipStream_t s);
+// its launches 1-3 alone: every parent a root, the statistics in the roots' slots
+hipError_t launch_mask_labelling(const ComponentsArgs& a, hipStream_t s);
+// the selection of components of a chunk labelled by launch_mask_labelling on
+// the same stream, and the word-wise logic of two masks (mask_select.hip)
+hipError_t launch_mask_select(const SelectArgs& a, hipStream_t s);
+hipError_t launch_mask_logic(const LogicArgs& a, hipStream_t s);
 // the links of a chunk of frames labelled by launch_mask_components on the
 // same stream (mask_tracks.hip): the clear of the overlap table and the four
 // launches, in order, on `s`

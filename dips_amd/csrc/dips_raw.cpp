@@ -62,6 +62,20 @@
 //            1 .. K, default the majority K / 2 + 1), over the whole clip in
 //            one call with clear frames before it, applied before --morph;
 //            the stdout line has vote=K,M; a bad value exits with status 2
+//            [--select [min-area=A][,max-area=B][,clear-border][,dropped]
+//            [,connectivity=4|8]] -> with what takes a mask: the components of
+//            the change mask that pass the predicate, with dips_mask_select
+//            (defaults 1, 0 = no upper bound, 8), applied after --vote and
+//            --morph; the stdout line has select=A,B,<flags>,<connectivity>
+//            [--hysteresis TAU_HIGH] -> likewise, only with the plain change
+//            mask (not with --background or --sigma-delta): of those
+//            components only the ones that hold a pixel of the change mask at
+//            TAU_HIGH >= --tau (a second handle), in the same
+//            dips_mask_select call; the stdout line has hysteresis=TAU_HIGH
+//            [--fill-holes [MAX]] -> likewise: after --select the holes of the
+//            mask (of at most MAX pixels; default 0: all) are filled with
+//            dips_mask_logic and dips_mask_select, under --select's
+//            connectivity; the stdout line has fill_holes=MAX
 //            [--background K[,selective] [--background-out FILE]] -> with
 //            --mask, --boxes or --tracks: the mask is taken against the running-average
 //            background with dips_diff_background_mask (rate_shift K in
@@ -79,7 +93,8 @@
 //            sigma_delta=N,VMIN,VMAX
 //            [--mask-counts FILE [--mask-grid RxC]] [--mask-times FILE]
 //            [--mask-sums FILE] -> the statistics of the final mask (behind
-//            --background / --sigma-delta, --vote and --morph; --roi as for
+//            --background / --sigma-delta, --vote, --morph, --select and
+//            --fill-holes; --roi as for
 //            --mask) with dips_mask_counts and dips_mask_pixel_times, with
 //            --mask, --boxes or --tracks or on their own (the stdout line then
 //            begins with "mask-stats" and no mask is written): the counts as
@@ -156,11 +171,14 @@ int usage() {
                  "                [--tracks FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
                  "                [--vote K[,M]] (with --mask, --boxes or --tracks; before --morph)\n"
                  "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask, --boxes or --tracks)\n"
+                 "                [--select [min-area=A][,max-area=B][,clear-border][,dropped][,connectivity=4|8]]\n"
+                 "                [--hysteresis TAU_HIGH] [--fill-holes [MAX]] (with what takes a mask, after --morph: select,\n"
+                 "                then fill-holes; the last two not with --background or --sigma-delta)\n"
                  "                [--background K[,selective] [--background-out FILE]] (with --mask, --boxes or --tracks)\n"
                  "                [--sigma-delta N[,VMIN[,VMAX]] [--sigma-delta-out FILE]] (likewise; not with --background)\n"
                  "                [--mask-counts FILE [--mask-grid RxC]] [--mask-times FILE] [--mask-sums FILE]\n"
                  "                (of the final mask; alone or with --mask, --boxes or --tracks; take --roi, --vote,\n"
-                 "                --morph, --background and --sigma-delta as --mask does)\n"
+                 "                --morph, --select, --hysteresis, --fill-holes, --background and --sigma-delta as --mask does)\n"
                  "       dips_raw sharded IN.raw W H rgb8|rgba8|gray8 --ranks N [--mode overall|per-frame]\n"
                  "                [--tau T] [--transport loopback|rccl]\n");
     return 1;
@@ -340,6 +358,104 @@ int apply_morph(dips_handle* hd, std::vector<uint8_t>& mask, uint32_t n, uint32_
         mask.swap(other);
     }
     return DIPS_OK;
+}
+
+// --select, --hysteresis, --fill-holes: the selection of components of the
+// final mask (dips_mask_select, dips_mask_logic).
+struct SelectOpt {
+    bool on = false;  // --select
+    uint32_t min_area = 1, max_area = 0, flags = 0, connectivity = 8;
+    bool hysteresis = false;
+    float tau_high = 0.0f;
+    bool fill = false;
+    uint32_t max_hole = 0;
+    bool any() const { return on || hysteresis || fill; }
+};
+
+// "[min-area=A][,max-area=B][,clear-border][,dropped][,connectivity=4|8]" -> the option
+bool parse_select(const std::string& s, SelectOpt* o) {
+    size_t at = 0;
+    while (at <= s.size()) {
+        const size_t comma = std::min(s.find(',', at), s.size());
+        const std::string item = s.substr(at, comma - at);
+        const size_t eq = item.find('=');
+        const std::string key = item.substr(0, eq), val = eq == std::string::npos ? "" : item.substr(eq + 1);
+        if (key == "min-area" && eq != std::string::npos) {
+            if (!parse_u32_or_zero(val.c_str(), &o->min_area)) return false;
+        } else if (key == "max-area" && eq != std::string::npos) {
+            if (!parse_u32_or_zero(val.c_str(), &o->max_area)) return false;
+        } else if (key == "connectivity" && eq != std::string::npos) {
+            if (!parse_u32(val.c_str(), &o->connectivity) || (o->connectivity != 4u && o->connectivity != 8u)) return false;
+        } else if (item == "clear-border") {
+            o->flags |= DIPS_SELECT_CLEAR_BORDER;
+        } else if (item == "dropped") {
+            o->flags |= DIPS_SELECT_DROPPED;
+        } else {
+            return false;
+        }
+        at = comma + 1;
+    }
+    o->on = true;
+    return o->max_area == 0u || o->max_area >= o->min_area;
+}
+
+// The selection, then the hole filling, on the host mask of n frames of rw x
+// rh pixels; the result is in `mask` again.  --hysteresis takes its marker,
+// the change mask of the same frames at tau_high, from a handle of its own;
+// a failure there is reported here and *what set to NULL.
+int apply_select(dips_handle* hd, const dips_params& p, uint32_t w, uint32_t h, const uint8_t* frames, uint32_t n,
+                 const uint32_t* roi, std::vector<uint8_t>& mask, uint32_t rw, uint32_t rh, const SelectOpt& o,
+                 const char** what) {
+    if (!o.any() || n == 0) return DIPS_OK;
+    std::vector<uint8_t> other(mask.size());
+    if (o.on || o.hysteresis) {
+        std::vector<uint8_t> strong;
+        if (o.hysteresis) {
+            dips_params ph = p;
+            ph.tau = o.tau_high;
+            dips_handle* hs = nullptr;
+            int st = dips_create(&ph, 0, &hs);
+            if (st == DIPS_OK) {
+                strong.resize(mask.size());
+                st = dips_diff_change_mask(hs, w, h, frames, n, nullptr, roi, strong.data());
+            }
+            if (st != DIPS_OK) {
+                lib_error(hs, hs ? "dips_diff_change_mask (--hysteresis)" : "dips_create (--hysteresis)", st);
+                *what = nullptr;
+            }
+            if (hs) dips_destroy(hs);
+            if (st != DIPS_OK) return st;
+        }
+        *what = "dips_mask_select";
+        const int st = dips_mask_select(hd, mask.data(), n, rw, rh, o.connectivity, o.min_area, o.max_area, o.flags,
+                                        o.hysteresis ? strong.data() : nullptr, o.hysteresis ? n : 0u, 0u, other.data(),
+                                        nullptr);
+        if (st != DIPS_OK) return st;
+        mask.swap(other);
+    }
+    if (o.fill) {
+        // the holes: the components of the complement, under the dual
+        // connectivity, that do not touch the border
+        std::vector<uint8_t> holes(mask.size());
+        *what = "dips_mask_logic";
+        int st = dips_mask_logic(hd, mask.data(), n, rw, rh, DIPS_LOGIC_NOT, nullptr, 0u, other.data());
+        if (st != DIPS_OK) return st;
+        *what = "dips_mask_select";
+        st = dips_mask_select(hd, other.data(), n, rw, rh, 12u - o.connectivity, 1u, o.max_hole, DIPS_SELECT_CLEAR_BORDER,
+                              nullptr, 0u, 0u, holes.data(), nullptr);
+        if (st != DIPS_OK) return st;
+        *what = "dips_mask_logic";
+        st = dips_mask_logic(hd, mask.data(), n, rw, rh, DIPS_LOGIC_OR, holes.data(), n, other.data());
+        if (st != DIPS_OK) return st;
+        mask.swap(other);
+    }
+    return DIPS_OK;
+}
+
+void print_select(const SelectOpt& o) {
+    if (o.on) std::printf(" select=%u,%u,%u,%u", o.min_area, o.max_area, o.flags, o.connectivity);
+    if (o.hysteresis) std::printf(" hysteresis=%g", (double)o.tau_high);
+    if (o.fill) std::printf(" fill_holes=%u", o.max_hole);
 }
 
 // --mask-counts [--mask-grid], --mask-times, --mask-sums: the statistics of
@@ -708,6 +824,7 @@ int run_series(int argc, char** argv) {
     bool has_box_opt = false;
     std::vector<MorphStep> morph;
     VoteOpt vote;
+    SelectOpt sel;
     BackgroundOpt bg;
     SigmaDeltaOpt sd;
     StatsOpt stats;
@@ -753,6 +870,16 @@ int run_series(int argc, char** argv) {
                 usage();
                 return 2;
             }
+        } else if (a == "--select" && has) {
+            if (!parse_select(argv[++i], &sel)) return usage();
+        } else if (a == "--hysteresis" && has) {
+            char* end = nullptr;
+            sel.tau_high = std::strtof(argv[++i], &end);
+            if (end == argv[i] || *end) return usage();
+            sel.hysteresis = true;
+        } else if (a == "--fill-holes") {
+            sel.fill = true;
+            if (has && parse_u32_or_zero(argv[i + 1], &sel.max_hole)) ++i;  // MAX is optional
         } else if (a == "--background" && has) {
             if (!parse_background(argv[++i], &bg)) return usage();
         } else if (a == "--background-out" && has) {
@@ -785,6 +912,10 @@ int run_series(int argc, char** argv) {
     if (!morph.empty() && !masked) return usage();
     // so does --vote
     if (vote.window != 0u && !masked) return usage();
+    // so do --select, --hysteresis and --fill-holes; the last two take the plain change mask only
+    if (sel.any() && !masked) return usage();
+    if ((sel.hysteresis || sel.fill) && (bg.on || sd.on)) return usage();
+    if (sel.hysteresis && !(sel.tau_high >= p.tau)) return usage();
     // --background too, --background-out to --background
     if ((bg.on && !masked) || (bg.out_path && !bg.on)) return usage();
     // so does --sigma-delta, --sigma-delta-out to --sigma-delta; the two models exclude each other
@@ -879,10 +1010,11 @@ int run_series(int argc, char** argv) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
         }
+        if (st == DIPS_OK) st = apply_select(hd, p, w, h, in.p, n, has_roi ? roi : nullptr, mask, rw, rh, sel, &what);
         StatsOut stats_out;
         if (st == DIPS_OK) st = mask_stats(hd, mask, n, rw, rh, stats, &stats_out, &what);
         if (st != DIPS_OK) {
-            const int rc = lib_error(hd, what, st);
+            const int rc = what ? lib_error(hd, what, st) : 2;  // NULL: reported already
             dips_destroy(hd);
             return rc;
         }
@@ -903,6 +1035,7 @@ int run_series(int argc, char** argv) {
                     has_roi ? roi[0] : 0u, has_roi ? roi[1] : 0u, rw, rh, n, row_bytes, set);
         if (vote.window != 0u) std::printf(" vote=%u,%u", vote.window, vote.votes);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
+        print_select(sel);
         print_background(bg, sd);
         print_mask_stats(stats);
         std::printf("\n");
@@ -934,6 +1067,7 @@ int run_series(int argc, char** argv) {
             what = "dips_mask_morph";
             st = apply_morph(hd, mask, n, rw, rh, morph);
         }
+        if (st == DIPS_OK) st = apply_select(hd, p, w, h, in.p, n, has_roi ? roi : nullptr, mask, rw, rh, sel, &what);
         if (st == DIPS_OK && tracks) {
             what = "dips_mask_tracks";
             st = dips_mask_tracks(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, nullptr, ids.data(),
@@ -946,7 +1080,7 @@ int run_series(int argc, char** argv) {
         StatsOut stats_out;
         if (st == DIPS_OK) st = mask_stats(hd, mask, n, rw, rh, stats, &stats_out, &what);
         if (st != DIPS_OK) {
-            const int rc = lib_error(hd, what, st);
+            const int rc = what ? lib_error(hd, what, st) : 2;  // NULL: reported already
             dips_destroy(hd);
             return rc;
         }
@@ -984,6 +1118,7 @@ int run_series(int argc, char** argv) {
         if (tracks) std::printf(" tracks=%u", ids[0]);
         if (vote.window != 0u) std::printf(" vote=%u,%u", vote.window, vote.votes);
         if (!morph.empty()) std::printf(" morph=%zu", morph.size());
+        print_select(sel);
         print_background(bg, sd);
         print_mask_stats(stats);
         std::printf("\n");

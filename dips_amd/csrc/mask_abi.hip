@@ -1,7 +1,8 @@
 // mask_abi.hip -- host side of include/dips_hip.h, part 5: the products of a
 // packed change mask -- its connected components, the components linked
-// across frames (tracks), the binary morphology, the temporal vote and the
-// statistics (grid counts, change times and per-pixel sums).  What
+// across frames (tracks), the binary morphology, the temporal vote, the
+// selection of components with the word-wise logic, and the statistics (grid
+// counts, change times and per-pixel sums).  What
 // they share with the series and the regional products is in series_host.h.
 // Every extern "C" body runs inside dips_abi::guard (abi_guard.h).
 #include <hip/hip_runtime.h>
@@ -293,18 +294,92 @@ dips_status run_vote_device(dips_handle* h, const uint8_t* mask_in, uint32_t n_f
 }
 
 // ---------------------------------------------------------------------------
-// The statistics of a mask (dips_mask_counts, dips_mask_pixel_times; kernels
-// in mask_stats.hip)
+// The selection of components of a mask and the logic of two masks
+// (dips_mask_select, dips_mask_logic; kernels in mask_components.hip and
+// mask_select.hip)
 // ---------------------------------------------------------------------------
-
-// the parts' summaries of dips_mask_pixel_times stay within this (the handle's times_parts)
-constexpr uint64_t kMaskTimesPartsBytes = 1ull << 30;
 
 // whether two byte ranges share a byte
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return a && b && na != 0 && nb != 0 && pa < pb + nb && pb < pa + na;
 }
+
+// Label the frames of a device mask and write the components selected,
+// asynchronously on `s`, `chunk` frames per round (0: automatic) in the
+// handle's scratch, laid out as run_components_device lays it out.  marker
+// NULL: none; else marker_frames (1 or n_frames) frames.  counts NULL: none.
+dips_status run_select_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                              uint32_t connectivity, uint32_t min_area, uint32_t max_area, uint32_t select,
+                              const uint8_t* marker, uint32_t marker_frames, uint32_t chunk, uint8_t* mask_out,
+                              uint32_t* counts, hipStream_t s) {
+    dips::SelectArgs g{};
+    dips::ComponentsArgs& a = g.cc;
+    a = components_args(w, hgt, connectivity, min_area);
+    g.max_area = max_area;
+    g.select = select;
+    g.marker_stride = marker && marker_frames != 1u ? a.wpf : 0u;
+    const size_t per_frame = 4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf;
+    uint64_t frames = chunk ? chunk : std::max<uint64_t>(1u, kComponentsScratchBytes / per_frame);
+    frames = std::min<uint64_t>(frames, n_frames);
+    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
+    const uint32_t F = (uint32_t)frames;
+    // the scratch before the timed span (growing it synchronises)
+    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F));
+    uint8_t* base = h->cc_scratch.as<uint8_t>();
+    a.sum_i = reinterpret_cast<uint64_t*>(base);
+    a.sum_j = a.sum_i + (size_t)F * a.nslots;
+    a.area = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);
+    a.min_x = a.area + (size_t)F * a.nslots;
+    a.max_x = a.min_x + (size_t)F * a.nslots;
+    a.max_y = a.max_x + (size_t)F * a.nslots;
+    a.parent = a.max_y + (size_t)F * a.nslots;
+    a.block_count = a.parent + (size_t)F * a.npx;
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    // the blocks of sel_write_kernel add onto the counts
+    if (counts) DIPS_HIP(h, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)n_frames, s));
+    const size_t frame_words = (size_t)a.wpf;
+    for (uint32_t t = 0; t < n_frames; t += F) {
+        a.n_frames = std::min(F, n_frames - t);
+        a.mask = reinterpret_cast<const uint32_t*>(mask) + (size_t)t * frame_words;
+        g.marker = marker ? reinterpret_cast<const uint32_t*>(marker) + (size_t)t * g.marker_stride : nullptr;
+        g.out = reinterpret_cast<uint32_t*>(mask_out) + (size_t)t * frame_words;
+        g.counts = counts ? counts + t : nullptr;
+        DIPS_HIP(h, dips::launch_mask_labelling(a, s));
+        DIPS_HIP(h, dips::launch_mask_select(g, s));
+    }
+    return span.end(s);
+}
+
+// The logic of two device masks, asynchronously on `s`: one launch.
+dips_status run_logic_device(dips_handle* h, const uint8_t* a_in, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                             uint32_t op, const uint8_t* b_in, uint32_t b_frames, uint8_t* mask_out, hipStream_t s) {
+    dips::LogicArgs g{};
+    g.a = reinterpret_cast<const uint32_t*>(a_in);
+    g.b = reinterpret_cast<const uint32_t*>(b_in);
+    g.out = reinterpret_cast<uint32_t*>(mask_out);
+    g.w = w;
+    g.wpr = (uint32_t)mask_words_per_row(w);
+    g.wpf = g.wpr * hgt;
+    g.words = (uint64_t)g.wpf * n_frames;
+    g.op = op;
+    g.b_bcast = b_in && b_frames == 1u && n_frames != 1u ? 1u : 0u;
+
+    KernelSpan span(h);
+    DIPS_TRY(span.begin(s));
+    DIPS_HIP(h, dips::launch_mask_logic(g, s));
+    return span.end(s);
+}
+
+// ---------------------------------------------------------------------------
+// The statistics of a mask (dips_mask_counts, dips_mask_pixel_times; kernels
+// in mask_stats.hip)
+// ---------------------------------------------------------------------------
+
+// the parts' summaries of dips_mask_pixel_times stay within this (the handle's times_parts)
+constexpr uint64_t kMaskTimesPartsBytes = 1ull << 30;
 
 // The grid counts of a device mask, asynchronously on `s`: the clear of
 // counts where several blocks add to a cell, and one launch.
@@ -659,6 +734,97 @@ dips_status dips_mask_vote(dips_handle* h, const uint8_t* mask_in, uint32_t n_fr
         if (bytes) DIPS_HIP(h, hipMemcpyAsync(mask_out, out_dev, bytes, hipMemcpyDeviceToHost, h->stream));
         if (history_out)
             DIPS_HIP(h, hipMemcpyAsync(history_out, out_dev + bytes, hist_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_select(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                             uint32_t connectivity, uint32_t min_area, uint32_t max_area, uint32_t select,
+                             const uint8_t* marker, uint32_t marker_frames, uint32_t chunk_frames, uint8_t* mask_out,
+                             uint32_t* counts) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask || !mask_out) return fail(h, DIPS_ERR_INVALID, "mask_select: null argument");
+        DIPS_TRY(check_labelling(h, "mask_select", n_frames, roi_w, roi_h, connectivity, 0u));
+        if ((select & ~(DIPS_SELECT_CLEAR_BORDER | DIPS_SELECT_DROPPED)) != 0u)
+            return fail(h, DIPS_ERR_INVALID, "mask_select: unknown bits in select");
+        if (max_area != 0u && max_area < min_area)
+            return fail(h, DIPS_ERR_INVALID, "mask_select: max_area must be 0 or at least min_area");
+        if (marker ? (marker_frames != 1u && marker_frames != n_frames) : marker_frames != 0u)
+            return fail(h, DIPS_ERR_INVALID,
+                        "mask_select: marker_frames must be 1 or n_frames with a marker and 0 without");
+        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        const size_t mask_bytes = frame_bytes * n_frames, marker_bytes = frame_bytes * marker_frames;
+        const size_t counts_bytes = counts ? sizeof(uint32_t) * (size_t)n_frames : 0u;
+        if (ranges_overlap(mask_out, mask_bytes, mask, mask_bytes) ||
+            ranges_overlap(mask_out, mask_bytes, marker, marker_bytes) ||
+            ranges_overlap(counts, counts_bytes, mask, mask_bytes) ||
+            ranges_overlap(counts, counts_bytes, marker, marker_bytes) ||
+            ranges_overlap(counts, counts_bytes, mask_out, mask_bytes))
+            return fail(h, DIPS_ERR_INVALID, "mask_select: an output must not overlap an input or the other output");
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_select", {mask, marker, mask_out, counts}));
+            return run_select_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_area, select, marker,
+                                     marker_frames, chunk_frames, mask_out, counts, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call); the marker
+        // behind the mask
+        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes + marker_bytes));
+        DIPS_HIP(h, h->stage_map.ensure(mask_bytes));
+        if (counts) DIPS_HIP(h, h->stage_series.ensure(counts_bytes));
+        uint8_t* mask_dev = h->stage_frames.as<uint8_t>();
+        uint8_t* marker_dev = marker ? mask_dev + mask_bytes : nullptr;
+        uint32_t* counts_dev = counts ? h->stage_series.as<uint32_t>() : nullptr;
+        DIPS_HIP(h, hipMemcpyAsync(mask_dev, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        if (marker) DIPS_HIP(h, hipMemcpyAsync(marker_dev, marker, marker_bytes, hipMemcpyHostToDevice, h->stream));
+        st = run_select_device(h, mask_dev, n_frames, roi_w, roi_h, connectivity, min_area, max_area, select,
+                               marker_dev, marker_frames, chunk_frames, h->stage_map.as<uint8_t>(), counts_dev,
+                               h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, mask_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (counts) DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_logic(dips_handle* h, const uint8_t* a, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                            uint32_t op, const uint8_t* b, uint32_t b_frames, uint8_t* mask_out) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!a || !mask_out) return fail(h, DIPS_ERR_INVALID, "mask_logic: null argument");
+        if (op > DIPS_LOGIC_NOT) return fail(h, DIPS_ERR_INVALID, "mask_logic: op must be 0 .. 4");
+        if (op == DIPS_LOGIC_NOT ? (b != nullptr || b_frames != 0u) : b == nullptr)
+            return fail(h, DIPS_ERR_INVALID, "mask_logic: NOT takes no b, every other op needs one");
+        if (b && b_frames != 1u && b_frames != n_frames)
+            return fail(h, DIPS_ERR_INVALID, "mask_logic: b_frames must be 1 or n_frames");
+        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_logic: roi_w and roi_h must not be 0");
+        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
+            return fail(h, DIPS_ERR_INVALID, "mask_logic: the region must stay below 2^30 pixels");
+        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        const size_t bytes = frame_bytes * n_frames, b_bytes = frame_bytes * b_frames;
+        if (ranges_overlap(mask_out, bytes, a, bytes) || ranges_overlap(mask_out, bytes, b, b_bytes))
+            return fail(h, DIPS_ERR_INVALID, "mask_logic: mask_out must not overlap an input");
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_logic", {a, b, mask_out}));
+            return run_logic_device(h, a, n_frames, roi_w, roi_h, op, b, b_frames, mask_out, h->stream);
+        }
+        // host pointers: stage through HBM (synchronous call); b behind a
+        DIPS_HIP(h, h->stage_frames.ensure(bytes + b_bytes));
+        DIPS_HIP(h, h->stage_map.ensure(bytes));
+        uint8_t* a_dev = h->stage_frames.as<uint8_t>();
+        uint8_t* b_dev = b ? a_dev + bytes : nullptr;
+        DIPS_HIP(h, hipMemcpyAsync(a_dev, a, bytes, hipMemcpyHostToDevice, h->stream));
+        if (b) DIPS_HIP(h, hipMemcpyAsync(b_dev, b, b_bytes, hipMemcpyHostToDevice, h->stream));
+        st = run_logic_device(h, a_dev, n_frames, roi_w, roi_h, op, b_dev, b_frames, h->stage_map.as<uint8_t>(),
+                              h->stream);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, bytes, hipMemcpyDeviceToHost, h->stream));
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

@@ -51,10 +51,18 @@
 // bounded by the row and by kBackWords.  Stale reads of parent are harmless:
 // every value a node ever held is a node of its own component, and only the
 // atomicMin's return decides whether a union is done.
+//
+// dips_mask_select runs launches 1-3 (launch_mask_labelling) and then its own
+// two (mask_select.hip).  Those add no new kind of loop: sel_mark_kernel's
+// run loop clears at least one bit of a word per step and its wave loop
+// retires at least its leader per step, like cc_stats_kernel's; its one
+// atomic is a fetch-or whose return nobody waits for; sel_write_kernel has
+// the run loop only.  Both read parent after launch 3, when it is final.
 #include <hip/hip_runtime.h>
 
 #include "dips_kernels.h"
-#include "mask_runs.h"  // next_run, local_start
+#include "mask_labelling.h"  // word_pos, mask_word, slot_of, ld_parent
+#include "mask_runs.h"       // next_run, local_start
 
 namespace dips {
 
@@ -62,36 +70,8 @@ namespace {
 
 constexpr uint32_t kBackWords = 64;  // all-ones words a continuing run walks back over
 
-__device__ __forceinline__ uint32_t ld_parent(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __device__ __forceinline__ void st_parent(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The thread's word of the chunk: frame f, row j, word k of the row; false
-// for the threads past the frame's last word.
-struct WordPos {
-    uint32_t f, j, k;
-    bool active;
-};
-
-__device__ __forceinline__ WordPos word_pos(const ComponentsArgs& a) {
-    WordPos q;
-    q.f = blockIdx.x / a.bpf;
-    const uint32_t wi = (blockIdx.x - q.f * a.bpf) * 256u + threadIdx.x;
-    q.active = wi < a.wpf;
-    q.j = q.active ? wi / a.wpr : 0u;
-    q.k = q.active ? wi - q.j * a.wpr : 0u;
-    return q;
-}
-
-// Word k of row j of frame f with the pad bits of the row's last word cleared.
-__device__ __forceinline__ uint32_t mask_word(const ComponentsArgs& a, uint32_t f, uint32_t j, uint32_t k) {
-    uint32_t v = a.mask[((size_t)f * a.h + j) * a.wpr + k];
-    if (k == a.wpr - 1u && (a.w & 31u) != 0u) v &= (1u << (a.w & 31u)) - 1u;
-    return v;
 }
 
 __device__ __forceinline__ uint32_t find_root(const uint32_t* parent, uint32_t x) {
@@ -118,10 +98,6 @@ __device__ __forceinline__ void unite(uint32_t* parent, uint32_t x, uint32_t y) 
         if (old == x) return;
         x = old;  // someone else hung x under old < x: unite old and y
     }
-}
-
-__device__ __forceinline__ size_t slot_of(const ComponentsArgs& a, uint32_t f, uint32_t j, uint32_t i) {
-    return (size_t)f * a.nslots + (size_t)j * a.hw + (i >> 1);
 }
 
 // Exclusive prefix sum of v over the block's 256 threads; *total = the sum.
@@ -359,19 +335,35 @@ __global__ __launch_bounds__(256) void cc_labels_kernel(ComponentsArgs a) {
     a.labels[t] = label;
 }
 
-hipError_t launch_mask_components(const ComponentsArgs& a, hipStream_t s) {
+// Whether `a` describes a chunk the labelling's launches can take.
+static bool labelling_args_ok(const ComponentsArgs& a) {
     const uint64_t word_blocks = (uint64_t)a.n_frames * a.bpf;
-    const uint64_t pixel_blocks = ((uint64_t)a.n_frames * a.npx + 255u) / 256u;
-    if (a.n_frames == 0 || a.w == 0 || a.h == 0 || a.npx != a.w * a.h || a.npx >= (1u << 30) ||
-        a.wpr != (a.w + 31u) / 32u || a.hw != (a.w + 1u) / 2u || a.nslots != a.hw * a.h || a.wpf != a.wpr * a.h ||
-        a.bpf != (a.wpf + 255u) / 256u || word_blocks >= (1ull << 31) || pixel_blocks >= (1ull << 31) ||
-        (a.connectivity != 4u && a.connectivity != 8u) || !a.mask || !a.parent || !a.sum_i || !a.sum_j || !a.area ||
-        !a.min_x || !a.max_x || !a.max_y || !a.block_count || !a.counts || (a.max_boxes != 0u && !a.boxes))
-        return hipErrorInvalidValue;
-    const dim3 wg((uint32_t)word_blocks), tb(256);
+    return !(a.n_frames == 0 || a.w == 0 || a.h == 0 || a.npx != a.w * a.h || a.npx >= (1u << 30) ||
+             a.wpr != (a.w + 31u) / 32u || a.hw != (a.w + 1u) / 2u || a.nslots != a.hw * a.h ||
+             a.wpf != a.wpr * a.h || a.bpf != (a.wpf + 255u) / 256u || word_blocks >= (1ull << 31) ||
+             (a.connectivity != 4u && a.connectivity != 8u) || !a.mask || !a.parent || !a.sum_i || !a.sum_j ||
+             !a.area || !a.min_x || !a.max_x || !a.max_y);
+}
+
+// Launches 1-3: afterwards every parent is a root and the root's slot holds
+// the component's statistics.
+hipError_t launch_mask_labelling(const ComponentsArgs& a, hipStream_t s) {
+    if (!labelling_args_ok(a)) return hipErrorInvalidValue;
+    const dim3 wg((uint32_t)((uint64_t)a.n_frames * a.bpf)), tb(256);
     hipLaunchKernelGGL(cc_rows_kernel, wg, tb, 0, s, a);
     hipLaunchKernelGGL(cc_merge_kernel, wg, tb, 0, s, a);
     hipLaunchKernelGGL(cc_stats_kernel, wg, tb, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mask_components(const ComponentsArgs& a, hipStream_t s) {
+    const uint64_t pixel_blocks = ((uint64_t)a.n_frames * a.npx + 255u) / 256u;
+    if (!labelling_args_ok(a) || pixel_blocks >= (1ull << 31) || !a.block_count || !a.counts ||
+        (a.max_boxes != 0u && !a.boxes))
+        return hipErrorInvalidValue;
+    const hipError_t e = launch_mask_labelling(a, s);
+    if (e != hipSuccess) return e;
+    const dim3 wg((uint32_t)((uint64_t)a.n_frames * a.bpf)), tb(256);
     hipLaunchKernelGGL(cc_count_kernel, wg, tb, 0, s, a);
     hipLaunchKernelGGL(cc_offsets_kernel, dim3(a.n_frames), tb, 0, s, a);
     hipLaunchKernelGGL(cc_select_kernel, wg, tb, 0, s, a);

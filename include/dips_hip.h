@@ -710,6 +710,82 @@ dips_status dips_mask_vote(dips_handle *h, const uint8_t *mask_in, uint32_t n_fr
                            const uint8_t *history_in, uint8_t *history_out,
                            uint8_t *mask_out);
 
+/* The selection of components of a change mask: the labelling's knowledge of
+ * which pixels belong to which object, given back as a mask (difference ->
+ * threshold -> vote -> morphology -> selection -> components / statistics).
+ * Area opening (drop the components below A pixels, leave the rest bit for
+ * bit), reconstruction by marker (keep the components that hold a set bit of
+ * another mask: hysteresis thresholding, zone queries, opening by
+ * reconstruction), border clearing and, with dips_mask_logic, hole filling.
+ * The reference has no counterpart.  It reads masks and writes a mask, so it
+ * serves every pixel format and every mask source, and the answer is exact.
+ * Input and output: mask, marker and mask_out in exactly
+ * dips_diff_change_mask's layout for a region roi_w x roi_h.  Frames are
+ * independent.  The components of frame t are those of dips_mask_components
+ * under the same connectivity (4 or 8).  A component C of frame t is kept iff
+ *   area(C) >= min_area  (0 and 1 keep all),
+ *   max_area == 0 or area(C) <= max_area,
+ *   marker == NULL or C contains a pixel whose marker bit is set,
+ *   DIPS_SELECT_CLEAR_BORDER is not set or C has no pixel in row 0, row
+ *   roi_h - 1, column 0 or column roi_w - 1.
+ * marker_frames is 1 or n_frames (0 with marker == NULL): with 1 the one
+ * marker frame serves every t, with n_frames frame t of the marker serves
+ * frame t of the mask.  A marker bit on a clear mask pixel has no effect.
+ * mask_out(t) is the union of the kept components of frame t; with
+ * DIPS_SELECT_DROPPED it is the mask minus that union, so the two outputs
+ * partition the mask.  The pad bits of mask and marker are ignored, whatever
+ * they hold; those of mask_out are written as 0, and every byte of mask_out
+ * is written.  counts (NULL: not produced): counts[t] = the kept components
+ * of frame t, with or without DIPS_SELECT_DROPPED.  With marker == NULL,
+ * select == 0 and max_area == 0, counts equals dips_mask_components' counts
+ * and mask_out the packing of that call's labels != 0.
+ * chunk_frames and the scratch as in dips_mask_components; the result does
+ * not depend on chunk_frames.  The labelling's three launches and one or two
+ * more; the time depends on the bits.
+ * DIPS_FLAG_DEVICE_PTRS: all pointers are device pointers, 4-byte aligned,
+ * the call asynchronous on the handle's stream; else host pointers of any
+ * alignment, staged through HBM, synchronous.  DIPS_FLAG_TIME_KERNEL: one
+ * entry for all launches of the call.  n_frames == 0: DIPS_OK, nothing
+ * written.  DIPS_ERR_INVALID, outputs untouched: connectivity not 4 or 8,
+ * roi_w or roi_h of 0 or >= 2^24, a region of 2^30 pixels or more, a null
+ * mask or mask_out, bits of select other than the two above, max_area != 0
+ * and max_area < min_area, a marker with marker_frames not 1 or n_frames, no
+ * marker with marker_frames != 0, a misaligned device pointer, and any
+ * overlap between the byte range of an output (mask_out: n_frames frames,
+ * counts: n_frames words) and that of an input or of the other output.
+ * DIPS_ERR_NOMEM if the scratch cannot be allocated. */
+#define DIPS_SELECT_CLEAR_BORDER 0x1u /* drop components with a pixel in row 0, row roi_h-1, column 0 or column roi_w-1 */
+#define DIPS_SELECT_DROPPED 0x2u      /* write mask \ kept instead of kept */
+dips_status dips_mask_select(dips_handle *h, const uint8_t *mask, uint32_t n_frames,
+                             uint32_t roi_w, uint32_t roi_h, uint32_t connectivity,
+                             uint32_t min_area, uint32_t max_area, uint32_t select,
+                             const uint8_t *marker, uint32_t marker_frames,
+                             uint32_t chunk_frames, uint8_t *mask_out, uint32_t *counts);
+
+/* Word-wise logic of masks: mask_out(t) = a(t) op b(t) inside the region, for
+ * the composites of the mask toolkit (a static zone mask ANDed onto every
+ * frame, the complement for hole filling, the union of a mask and its filled
+ * holes).  a, b and mask_out in exactly dips_diff_change_mask's layout for a
+ * region roi_w x roi_h; b_frames is 1 (the one frame of b serves every t) or
+ * n_frames; DIPS_LOGIC_NOT takes no b (b NULL, b_frames 0).  The pad bits of
+ * the inputs are ignored, whatever they hold; those of mask_out are written
+ * as 0 (DIPS_LOGIC_NOT of a clear frame has exactly roi_w bits per row), and
+ * every byte of mask_out is written.  One launch, no scratch; the time does
+ * not depend on the bits.  Pointer kinds, DIPS_FLAG_TIME_KERNEL and n_frames
+ * == 0 as in dips_mask_select.  DIPS_ERR_INVALID, mask_out untouched: a null
+ * a or mask_out, op > 4, DIPS_LOGIC_NOT with b or b_frames != 0, another op
+ * without b, b_frames not 1 or n_frames, roi_w or roi_h of 0, a region of
+ * 2^30 pixels or more, a misaligned device pointer, mask_out overlapping a or
+ * b. */
+#define DIPS_LOGIC_AND 0u
+#define DIPS_LOGIC_OR 1u
+#define DIPS_LOGIC_XOR 2u
+#define DIPS_LOGIC_ANDNOT 3u /* a & ~b */
+#define DIPS_LOGIC_NOT 4u    /* ~a inside the region; b must be NULL */
+dips_status dips_mask_logic(dips_handle *h, const uint8_t *a, uint32_t n_frames,
+                            uint32_t roi_w, uint32_t roi_h,
+                            uint32_t op, const uint8_t *b, uint32_t b_frames, uint8_t *mask_out);
+
 /* The statistics of a change mask: what dips_diff_series_grid,
  * dips_diff_pixel_sums and dips_diff_pixel_times give for the raw decision
  * |dI| > tau, for any mask -- one taken against a background model, or

@@ -55,6 +55,13 @@ pub const DIPS_MORPH_BOX: u32 = 0;
 pub const DIPS_MORPH_DIAMOND: u32 = 1;
 pub const DIPS_MORPH_MAX_RADIUS: u32 = 15;
 pub const DIPS_VOTE_MAX_WINDOW: u32 = 31;
+pub const DIPS_SELECT_CLEAR_BORDER: u32 = 0x1;
+pub const DIPS_SELECT_DROPPED: u32 = 0x2;
+pub const DIPS_LOGIC_AND: u32 = 0;
+pub const DIPS_LOGIC_OR: u32 = 1;
+pub const DIPS_LOGIC_XOR: u32 = 2;
+pub const DIPS_LOGIC_ANDNOT: u32 = 3;
+pub const DIPS_LOGIC_NOT: u32 = 4;
 pub const DIPS_BG_SELECTIVE: u32 = 1;
 pub const DIPS_BG_MAX_RATE_SHIFT: u32 = 8;
 pub const DIPS_SD_MAX_AMP: u32 = 15;
@@ -218,6 +225,11 @@ extern "C" {
                            shape: u32, rx: u32, ry: u32, mask_out: *mut u8) -> DipsStatus;
     pub fn dips_mask_vote(h: *mut DipsHandle, mask_in: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, window: u32,
                           votes: u32, history_in: *const u8, history_out: *mut u8, mask_out: *mut u8) -> DipsStatus;
+    pub fn dips_mask_select(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32,
+                            connectivity: u32, min_area: u32, max_area: u32, select: u32, marker: *const u8,
+                            marker_frames: u32, chunk_frames: u32, mask_out: *mut u8, counts: *mut u32) -> DipsStatus;
+    pub fn dips_mask_logic(h: *mut DipsHandle, a: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, op: u32,
+                           b: *const u8, b_frames: u32, mask_out: *mut u8) -> DipsStatus;
     pub fn dips_mask_counts(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, rows: u32,
                             cols: u32, counts: *mut u32) -> DipsStatus;
     pub fn dips_mask_pixel_times(h: *mut DipsHandle, mask: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, t0: u32,
