@@ -48,6 +48,10 @@ LINK_WORDS = 4  # DIPS_LINK_WORDS; the fields in the order of DIPS_LINK_PREV .. 
 LINK_FIELDS = ("prev", "overlap", "track", "age")
 LINK_NONE = 0xFFFFFFFF  # DIPS_LINK_NONE
 TRACK_MAX_BOXES = 256  # DIPS_TRACK_MAX_BOXES
+SHAPE_WORDS = 16  # DIPS_SHAPE_WORDS; the word offsets of DIPS_SHAPE_SX .. DIPS_SHAPE_EULER (64-bit fields: low, high)
+SHAPE_OFFSETS = {"sx": 0, "sy": 2, "sxx": 4, "syy": 6, "sxy": 8, "wsum": 10, "wmax": 12, "cracks_v": 13,
+                 "cracks_h": 14, "euler": 15}
+SHAPE_MAX_SIDE = 65536  # roi_w and roi_h of dips_mask_shapes
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # DIPS_MORPH_ERODE .. DIPS_MORPH_CLOSE
 MORPH_BOX, MORPH_DIAMOND = 0, 1  # DIPS_MORPH_BOX, DIPS_MORPH_DIAMOND
 MORPH_MAX_RADIUS = 15  # DIPS_MORPH_MAX_RADIUS
@@ -206,6 +210,7 @@ def load() -> ctypes.CDLL:
             "dips_diff_sigma_delta_mask": ([_vp, u32, u32, _u8p, u32, _u8p, P(u32), u32, u32, u32, u32, _vp, _u8p], st),
             "dips_mask_components": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _vp, _vp, _vp], st),
             "dips_mask_tracks": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, _vp, _vp, _vp, _vp], st),
+            "dips_mask_shapes": ([_vp, _u8p, _u8p, u32, u32, u32, u32, u32, u32, u32, _vp, _vp, _vp], st),
             "dips_mask_morph": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p], st),
             "dips_mask_vote": ([_vp, _u8p, u32, u32, u32, u32, u32, _u8p, _u8p, _u8p], st),
             "dips_mask_select": ([_vp, _u8p, u32, u32, u32, u32, u32, u32, u32, _u8p, u32, u32, _u8p, _vp], st),

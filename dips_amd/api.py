@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes
 import enum
+import math
 from dataclasses import dataclass
 from typing import Callable, Iterable, Iterator, List, Optional, Tuple
 
@@ -742,6 +743,181 @@ def _tracks_args(connectivity, min_area, max_boxes, chunk_frames, n: int) -> Tup
     return conn, area, k, chunk
 
 
+@dataclass
+class ChangeShapes:
+    """The shape records of the components of a change mask
+    (dips_mask_shapes): `counts` and `boxes` as in ChangeBoxes; `shapes`
+    uint32 [n, K, 16], record k of frame t the exact sums over the pixels
+    (i, j) of the component of box record k (OFFSETS: sx, sy, sxx, syy, sxy
+    and wsum as 64-bit fields of two words, wmax, cracks_v, cracks_h, euler),
+    zeros past min(counts[t], K).  The integer accessors are [n, K] arrays
+    over all records; the derived float64 properties are [n, K] too, NaN
+    where there is no record."""
+    counts: np.ndarray
+    boxes: np.ndarray
+    shapes: np.ndarray
+
+    OFFSETS = _lib.SHAPE_OFFSETS
+
+    def frame(self, t: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(uint32 [m, 8], uint32 [m, 16]): the m = min(counts[t], K) valid
+        records of frame t and their shapes."""
+        m = min(int(self.counts[t]), self.boxes.shape[1])
+        return self.boxes[t, :m], self.shapes[t, :m]
+
+    @property
+    def valid(self) -> np.ndarray:
+        """bool [n, K]: the records that describe a component."""
+        k = self.boxes.shape[1]
+        return np.arange(k, dtype=np.int64)[None, :] < np.minimum(self.counts.astype(np.int64), k)[:, None]
+
+    def _u64(self, name: str) -> np.ndarray:
+        f = self.OFFSETS[name]
+        return self.shapes[..., f].astype(np.uint64) | (self.shapes[..., f + 1].astype(np.uint64) << np.uint64(32))
+
+    @property
+    def area(self) -> np.ndarray:
+        return self.boxes[..., _lib.BOX_FIELDS.index("area")]
+
+    @property
+    def sx(self) -> np.ndarray:
+        return self._u64("sx")
+
+    @property
+    def sy(self) -> np.ndarray:
+        return self._u64("sy")
+
+    @property
+    def sxx(self) -> np.ndarray:
+        return self._u64("sxx")
+
+    @property
+    def syy(self) -> np.ndarray:
+        return self._u64("syy")
+
+    @property
+    def sxy(self) -> np.ndarray:
+        return self._u64("sxy")
+
+    @property
+    def wsum(self) -> np.ndarray:
+        return self._u64("wsum")
+
+    @property
+    def wmax(self) -> np.ndarray:
+        return self.shapes[..., self.OFFSETS["wmax"]]
+
+    @property
+    def perimeter(self) -> np.ndarray:
+        """uint32: the crack perimeter, cracks_v + cracks_h."""
+        return self.shapes[..., self.OFFSETS["cracks_v"]] + self.shapes[..., self.OFFSETS["cracks_h"]]
+
+    @property
+    def euler(self) -> np.ndarray:
+        """int32: 1 - holes."""
+        return np.ascontiguousarray(self.shapes[..., self.OFFSETS["euler"]]).view(np.int32)
+
+    @property
+    def holes(self) -> np.ndarray:
+        """int32: the holes of every record's component (0 where there is no record)."""
+        return np.where(self.valid, 1 - self.euler, 0).astype(np.int32)
+
+    def _central(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(A, N20, N02, N11) as object arrays of Python integers: A*SXX -
+        SX^2, A*SYY - SY^2 and A*SXY - SX*SY, formed exactly."""
+        a, sx, sy = self.area.astype(object), self.sx.astype(object), self.sy.astype(object)
+        return (a, a * self.sxx.astype(object) - sx * sx, a * self.syy.astype(object) - sy * sy,
+                a * self.sxy.astype(object) - sx * sy)
+
+    def _ratio(self, num, den) -> np.ndarray:
+        """float64 num / den of two object arrays where there is a record, NaN elsewhere."""
+        out = np.full(self.valid.shape, np.nan)
+        for idx in zip(*np.nonzero(self.valid)):
+            out[idx] = num[idx] / den[idx]  # Python integers: correctly rounded
+        return out
+
+    @property
+    def mu20(self) -> np.ndarray:
+        a, n20, _, _ = self._central()
+        return self._ratio(n20, a * a)
+
+    @property
+    def mu02(self) -> np.ndarray:
+        a, _, n02, _ = self._central()
+        return self._ratio(n02, a * a)
+
+    @property
+    def mu11(self) -> np.ndarray:
+        a, _, _, n11 = self._central()
+        return self._ratio(n11, a * a)
+
+    @property
+    def orientation(self) -> np.ndarray:
+        """The angle of the major axis, from +x towards +y in image
+        coordinates (y down), in (-pi/2, pi/2]: 0.5 * atan2(2 N11, N20 -
+        N02); 0 for an isotropic component."""
+        _, n20, n02, n11 = self._central()
+        out = np.full(self.valid.shape, np.nan)
+        for idx in zip(*np.nonzero(self.valid)):
+            out[idx] = 0.5 * math.atan2(float(2 * n11[idx]), float(n20[idx] - n02[idx]))
+        return out
+
+    @property
+    def axes(self) -> np.ndarray:
+        """float64 [n, K, 2]: the major and the minor axis, 4 * sqrt of the
+        eigenvalues of the covariance [[mu20, mu11], [mu11, mu02]] (the full
+        lengths of the ellipse with the same second moments)."""
+        m20, m02, m11 = self.mu20, self.mu02, self.mu11
+        mean, dev = 0.5 * (m20 + m02), np.sqrt(0.25 * (m20 - m02) ** 2 + m11 ** 2)
+        return np.stack([4.0 * np.sqrt(mean + dev), 4.0 * np.sqrt(np.maximum(mean - dev, 0.0))], axis=-1)
+
+    @property
+    def eccentricity(self) -> np.ndarray:
+        """sqrt(1 - minor^2 / major^2) of `axes`; 0 for a single pixel."""
+        ax = self.axes
+        major, minor = ax[..., 0], ax[..., 1]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            e = np.sqrt(np.maximum(1.0 - (minor / major) ** 2, 0.0))
+        return np.where(major == 0.0, 0.0, e)
+
+    @property
+    def compactness(self) -> np.ndarray:
+        """perimeter^2 / (4 pi area): 4 / pi for a square, larger the more ragged."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c = self.perimeter.astype(np.float64) ** 2 / (4.0 * math.pi * self.area.astype(np.float64))
+        return np.where(self.valid, c, np.nan)
+
+    @property
+    def mean_weight(self) -> np.ndarray:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = self.wsum.astype(np.float64) / self.area.astype(np.float64)
+        return np.where(self.valid, m, np.nan)
+
+    def as_arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        return self.counts, self.boxes, self.shapes
+
+    @classmethod
+    def from_arrays(cls, counts, boxes, shapes) -> "ChangeShapes":
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        boxes = np.ascontiguousarray(boxes, dtype=np.uint32)
+        shapes = np.ascontiguousarray(shapes, dtype=np.uint32)
+        if counts.ndim != 1 or boxes.ndim != 3 or boxes.shape[0] != counts.shape[0] or boxes.shape[2] != _lib.BOX_WORDS:
+            raise ValueError("counts must be [n] and boxes [n, K, 8]")
+        if shapes.shape != boxes.shape[:2] + (_lib.SHAPE_WORDS,):
+            raise ValueError("shapes must be [n, K, 16]")
+        return cls(counts, boxes, shapes)
+
+
+def _shapes_args(connectivity, min_area, max_boxes, chunk_frames, n: int, w: int, h: int) -> Tuple[int, int, int, int]:
+    """The scalar arguments of dips_mask_shapes over a region w x h, checked."""
+    conn, area, k, chunk = _components_args(connectivity, min_area, max_boxes, chunk_frames, n)
+    if w > _lib.SHAPE_MAX_SIDE or h > _lib.SHAPE_MAX_SIDE:
+        raise ValueError(f"the region's width and height must be at most {_lib.SHAPE_MAX_SIDE}")
+    if n * k * _lib.SHAPE_WORDS >= 1 << 32:
+        raise ValueError("n_frames * max_boxes * 16 must stay below 2^32")
+    return conn, area, k, chunk
+
+
 def _morph_args(op, shape, rx, ry, w: int, h: int) -> Tuple[int, int, int, int]:
     """The scalar arguments of dips_mask_morph, checked; ry None means rx."""
     try:
@@ -1411,6 +1587,70 @@ class DiffSeriesOperator:
                 boxes_out.data_ptr() if boxes_out is not None and boxes_out.numel() else None,
                 labels_out.data_ptr() if labels_out is not None and labels_out.numel() else None))
 
+    # -- the shape records of the components (dips_mask_shapes) ---------------
+    def mask_shapes(self, mask: ChangeMask, weights: Optional[np.ndarray] = None, connectivity: int = 8,
+                    min_area: int = 1, max_boxes: int = 64, chunk_frames: int = 0) -> ChangeShapes:
+        """mask_components of every frame of `mask`, and per record the exact
+        moments, crack counts and Euler number of its component; with
+        `weights` (uint8 [n, h, width], one value per pixel of the region)
+        also their sum and peak over it.  A mask that lives on the device
+        goes through run_mask_shapes_device."""
+        bits, rw, rh, n = _mask_host_args(mask)
+        conn, area, k, chunk = _shapes_args(connectivity, min_area, max_boxes, chunk_frames, n, rw, rh)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights)
+            if weights.dtype != np.uint8 or weights.shape != (n, rh, rw):
+                raise ValueError("weights must be uint8 [n, h, width]")
+        counts = np.zeros(n, dtype=np.uint32)
+        boxes = np.zeros((n, k, _lib.BOX_WORDS), dtype=np.uint32)
+        shapes = np.zeros((n, k, _lib.SHAPE_WORDS), dtype=np.uint32)
+        self._host.check(self._host._lib.dips_mask_shapes(
+            self._host.ptr, bits.ctypes.data if bits.size else None,
+            weights.ctypes.data if weights is not None and weights.size else None, n, rw, rh, conn, area, k, chunk,
+            counts.ctypes.data if n else None, boxes.ctypes.data if boxes.size else None,
+            shapes.ctypes.data if shapes.size else None))
+        return ChangeShapes(counts, boxes, shapes)
+
+    def run_mask_shapes_device(self, mask, width: int, counts_out, boxes_out, shapes_out, weights=None,
+                               connectivity: int = 8, min_area: int = 1, chunk_frames: int = 0, stream=None) -> None:
+        """Asynchronous: mask a uint8 device tensor [N, h, row_bytes] as
+        run_change_mask_device writes it for a region `width` pixels wide;
+        counts_out [N], boxes_out [N, K, 8] and shapes_out [N, K, 16] 4-byte
+        device tensors (both None: counts only), every element of them
+        written; counts_out and boxes_out 4-byte aligned, shapes_out 8-byte
+        aligned; weights (None: none) a uint8 device tensor [N, h, width] at
+        any alignment."""
+        import torch
+        rw, rh, n = _mask_device_args(mask, width)
+        if (boxes_out is None) != (shapes_out is None):
+            raise ValueError("boxes_out and shapes_out go together")
+        k = 0
+        if boxes_out is not None:
+            if boxes_out.dim() != 3 or boxes_out.shape[0] != n or boxes_out.shape[2] != _lib.BOX_WORDS:
+                raise ValueError("boxes_out must be a 4-byte tensor of shape [N, K, 8]")
+            k = int(boxes_out.shape[1])
+            if tuple(shapes_out.shape) != (n, k, _lib.SHAPE_WORDS):
+                raise ValueError("shapes_out must be a 4-byte tensor of shape [N, K, 16]")
+        conn, area, k, chunk = _shapes_args(connectivity, min_area, k, chunk_frames, n, rw, rh)
+        if tuple(counts_out.shape) != (n,):
+            raise ValueError("counts_out must be a 4-byte tensor of shape [N]")
+        if weights is not None and (weights.dtype != torch.uint8 or tuple(weights.shape) != (n, rh, rw)):
+            raise ValueError("weights must be a uint8 tensor of shape [N, h, width]")
+        for t in (counts_out, boxes_out, shapes_out):
+            if t is not None and t.element_size() != 4:
+                raise ValueError("counts_out, boxes_out and shapes_out must be 4-byte tensors")
+        for t in (mask, weights, counts_out, boxes_out, shapes_out):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device path needs contiguous HIP tensors")
+        lib = self._dev._lib
+        with _stream_of(self._dev, mask, stream):
+            self._dev.check(lib.dips_mask_shapes(
+                self._dev.ptr, mask.data_ptr() if mask.numel() else None,
+                weights.data_ptr() if weights is not None and weights.numel() else None, n, rw, rh, conn, area, k,
+                chunk, counts_out.data_ptr() if n else None,
+                boxes_out.data_ptr() if boxes_out is not None and boxes_out.numel() else None,
+                shapes_out.data_ptr() if shapes_out is not None and shapes_out.numel() else None))
+
     # -- the components linked across frames (dips_mask_tracks) ---------------
     def mask_tracks(self, mask: ChangeMask, connectivity: int = 8, min_area: int = 1, max_boxes: int = 64,
                     chunk_frames: int = 0, prev: Optional[np.ndarray] = None,
@@ -1996,7 +2236,7 @@ class DiffSeriesOperator:
 
     def change_boxes(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
                      max_boxes: int = 64, labels: bool = False, morph=None, background=None,
-                     sigma_delta=None, vote=None, select=None) -> ChangeBoxes:
+                     sigma_delta=None, vote=None, select=None, shapes: bool = False):
         """change_mask, then mask_components, with the mask kept on the
         device between the two: the moving objects of every frame.  frames /
         ref: numpy arrays (uploaded once) or uint8 device tensors.  morph: a
@@ -2014,8 +2254,13 @@ class DiffSeriesOperator:
         connectivity and fill_holes (True, or the largest hole to fill):
         after the morph steps the mask becomes mask_select's of it, then
         mask_fill_holes' of that, so that the pixels of the components
-        dropped leave the mask and not only the records."""
+        dropped leave the mask and not only the records.  shapes=True
+        returns (ChangeBoxes, ChangeShapes): the records come from
+        mask_shapes (no weights) instead of mask_components, so the mask is
+        still labelled once; it has no label image, so it excludes labels."""
         import torch
+        if shapes and labels:
+            raise ValueError("shapes=True produces no label image")
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
             lambda n_: _components_args(connectivity, min_area, max_boxes, 0, n_), sigma_delta, vote, select)
@@ -2023,20 +2268,29 @@ class DiffSeriesOperator:
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         boxes = torch.empty((n, k, _lib.BOX_WORDS), dtype=torch.int32, device=dev)
         lab = torch.empty((n, rh, rw), dtype=torch.int32, device=dev) if labels else None
-        self.run_mask_components_device(mask, rw, counts, boxes, lab, connectivity=connectivity, min_area=min_area)
 
         def to_u32(t):
             return t.cpu().numpy().view(np.uint32)  # the copy waits for the stream
 
+        if shapes:
+            rec = torch.empty((n, k, _lib.SHAPE_WORDS), dtype=torch.int32, device=dev)
+            self.run_mask_shapes_device(mask, rw, counts, boxes, rec, connectivity=connectivity, min_area=min_area)
+            counts, boxes = to_u32(counts), to_u32(boxes)
+            return ChangeBoxes(counts, boxes, None), ChangeShapes(counts, boxes, to_u32(rec))
+        self.run_mask_components_device(mask, rw, counts, boxes, lab, connectivity=connectivity, min_area=min_area)
         return ChangeBoxes(to_u32(counts), to_u32(boxes), to_u32(lab) if lab is not None else None)
 
     def change_tracks(self, frames, roi=None, ref=None, connectivity: int = 8, min_area: int = 1,
                       max_boxes: int = 64, morph=None, background=None, sigma_delta=None,
-                      vote=None, select=None) -> ChangeTracks:
+                      vote=None, select=None, shapes: bool = False):
         """change_mask, then mask_tracks, with the mask kept on the device
         between the two: the moving objects of every frame and their
         identity from frame to frame.  The arguments are change_boxes'; the
-        state of the result continues the ids in a later mask_tracks call."""
+        state of the result continues the ids in a later mask_tracks call.
+        shapes=True returns (ChangeTracks, ChangeShapes), shapes record k of
+        frame t describing the component of link record k; the shapes come
+        from a mask_shapes call (no weights) in addition to mask_tracks, so
+        the mask is labelled twice."""
         import torch
         mask, rw, rh, n = self._change_mask_on_device(
             frames, roi, ref, morph, background,
@@ -2052,7 +2306,12 @@ class DiffSeriesOperator:
         def to_u32(t):
             return t.cpu().numpy().view(np.uint32)  # the copy waits for the stream
 
-        return ChangeTracks(to_u32(counts), to_u32(boxes), to_u32(links), to_u32(state))
+        tracks = ChangeTracks(to_u32(counts), to_u32(boxes), to_u32(links), to_u32(state))
+        if not shapes:
+            return tracks
+        rec = torch.empty((n, k, _lib.SHAPE_WORDS), dtype=torch.int32, device=dev)
+        self.run_mask_shapes_device(mask, rw, counts, boxes, rec, connectivity=connectivity, min_area=min_area)
+        return tracks, ChangeShapes(tracks.counts, tracks.boxes, to_u32(rec))
 
     # -- the change times per pixel (dips_diff_pixel_times) --------------------
     def pixel_times(self, frames: np.ndarray, roi=None, ref: Optional[np.ndarray] = None, t0: int = 0,
@@ -2260,7 +2519,7 @@ def si_from_fixed(si_fixed) -> np.ndarray:
 
 __all__ = [
     "DiPsFilter", "ChromaFilter", "PixelFormat", "Mode", "DiPsProperties", "ComputeState",
-    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "ChangeTracks", "Background", "SigmaDelta", "mask_row_bytes", "grid_cell",
+    "frame_callback", "perform_dips_frames", "Series", "GridSeries", "PixelSums", "PixelTimes", "ChangeMask", "ChangeBoxes", "ChangeTracks", "ChangeShapes", "Background", "SigmaDelta", "mask_row_bytes", "grid_cell",
     "DiffSeriesOperator",
     "diff_series",
     "si_from_fixed", "VideoPathNotSpecifiedError", "FrameCallbackNotSpecifiedError", "DipsError",

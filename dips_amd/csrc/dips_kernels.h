@@ -383,6 +383,15 @@ struct SelectArgs {
     uint32_t select;         // DIPS_SELECT_* bits
 };
 
+// The shape records of a chunk of labelled mask frames (mask_shapes.hip),
+// behind launch_mask_components on the same stream with the same
+// ComponentsArgs `cc` (max_boxes > 0).
+struct ShapesArgs {
+    ComponentsArgs cc;
+    const uint8_t* weights;  // NULL: none; else the chunk's planes, npx bytes each, any alignment
+    uint32_t* shapes;        // the chunk's part, n_frames * max_boxes records; 8-byte aligned, cleared by the host
+};
+
 // Word-wise logic on mask frames (mask_select.hip): one launch, grid stride.
 struct LogicArgs {
     const uint32_t* a;   // n_frames frames of wpf words
@@ -730,6 +739,9 @@ hipError_t launch_mask_labelling(const ComponentsArgs& a, hipStream_t s);
 // the same stream, and the word-wise logic of two masks (mask_select.hip)
 hipError_t launch_mask_select(const SelectArgs& a, hipStream_t s);
 hipError_t launch_mask_logic(const LogicArgs& a, hipStream_t s);
+// the shape records of a chunk labelled by launch_mask_components on the same
+// stream (mask_shapes.hip): one launch
+hipError_t launch_mask_shapes(const ShapesArgs& a, hipStream_t s);
 // the links of a chunk of frames labelled by launch_mask_components on the
 // same stream (mask_tracks.hip): the clear of the overlap table and the four
 // launches, in order, on `s`

@@ -51,6 +51,14 @@
 //            columns prev,overlap,track,age behind every record (4294967295:
 //            none); the stdout line begins with "tracks" and ends with
 //            tracks=<ids handed out>
+//            [--shapes [--shape-weights FILE.raw]] -> with --boxes or --tracks:
+//            the shape record of every component with dips_mask_shapes
+//            (--boxes: instead of dips_mask_components; --tracks: in addition
+//            to dips_mask_tracks): the columns sx,sy,sxx,syy,sxy,wsum,wmax,
+//            cracks_v,cracks_h,euler behind every record; FILE.raw is the
+//            weight of every pixel, frames x roi_h x roi_w raw u8 planes of the
+//            region (without it wsum and wmax are 0); the stdout line ends
+//            with shapes=1
 //            [--morph erode|dilate|open|close:box|diamond:RXxRY]... -> with
 //            --mask, --boxes or --tracks: the binary morphology of the change mask with
 //            dips_mask_morph (radii 0 .. 15, a diamond needs RX = RY), the steps
@@ -169,6 +177,7 @@ int usage() {
                  "                [--mask FILE [--roi x,y,w,h]] [--pixel-times FILE [--roi x,y,w,h]]\n"
                  "                [--boxes FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
                  "                [--tracks FILE [--connectivity 4|8] [--min-area A] [--max-boxes K] [--roi x,y,w,h]]\n"
+                 "                [--shapes [--shape-weights FILE.raw]] (with --boxes or --tracks)\n"
                  "                [--vote K[,M]] (with --mask, --boxes or --tracks; before --morph)\n"
                  "                [--morph erode|dilate|open|close:box|diamond:RXxRY]... (with --mask, --boxes or --tracks)\n"
                  "                [--select [min-area=A][,max-area=B][,clear-border][,dropped][,connectivity=4|8]]\n"
@@ -822,6 +831,8 @@ int run_series(int argc, char** argv) {
     const char* tracks_path = nullptr;
     uint32_t connectivity = 8, min_area = 1, max_boxes = 64;
     bool has_box_opt = false;
+    bool shapes = false;
+    const char* shape_weights_path = nullptr;
     std::vector<MorphStep> morph;
     VoteOpt vote;
     SelectOpt sel;
@@ -861,6 +872,10 @@ int run_series(int argc, char** argv) {
             uint32_t* v = a == "--connectivity" ? &connectivity : a == "--min-area" ? &min_area : &max_boxes;
             if (!parse_u32_or_zero(argv[++i], v)) return usage();
             has_box_opt = true;
+        } else if (a == "--shapes") {
+            shapes = true;
+        } else if (a == "--shape-weights" && has) {
+            shape_weights_path = argv[++i];
         } else if (a == "--morph" && has) {
             MorphStep m{};
             if (!parse_morph(argv[++i], &m)) return usage();
@@ -926,6 +941,8 @@ int run_series(int argc, char** argv) {
             (boxes_path != nullptr) + (tracks_path != nullptr) > 1)
         return usage();
     if (has_box_opt && !boxes_path && !tracks_path) return usage();
+    // --shapes belongs to --boxes or --tracks, --shape-weights to --shapes
+    if ((shapes && !boxes_path && !tracks_path) || (shape_weights_path && !shapes)) return usage();
     if (connectivity != 4u && connectivity != 8u) return usage();
     Mapped in;
     if (!in.open(argv[2])) {
@@ -1051,10 +1068,19 @@ int run_series(int argc, char** argv) {
         const bool sane = dips_grid_cell(w, h, has_roi ? roi : nullptr, 1u, 1u, 0u, 0u, rect) == DIPS_OK &&
                           (uint64_t)rw * rh < (1ull << 30) && rw < (1u << 24) && rh < (1u << 24) &&
                           (uint64_t)n * max_boxes * DIPS_BOX_WORDS < (1ull << 32) &&
-                          (!tracks || max_boxes <= DIPS_TRACK_MAX_BOXES);
+                          (!tracks || max_boxes <= DIPS_TRACK_MAX_BOXES) &&
+                          (!shapes || (rw <= 65536u && rh <= 65536u &&
+                                       (uint64_t)n * max_boxes * DIPS_SHAPE_WORDS < (1ull << 32)));
+        Mapped weights;
+        if (shape_weights_path && (!weights.open(shape_weights_path) || weights.n != (size_t)n * rw * rh)) {
+            std::fprintf(stderr, "dips_raw: %s is not %u planes of %ux%u bytes\n", shape_weights_path, n, rw, rh);
+            dips_destroy(hd);
+            return 1;
+        }
         std::vector<uint8_t> mask(sane ? (size_t)n * rh * dips_mask_row_bytes(rw) : 1u);
         std::vector<uint32_t> counts(sane ? (size_t)n : 1u), recs(sane ? (size_t)n * max_boxes * DIPS_BOX_WORDS : 1u);
         std::vector<uint32_t> links(sane && tracks ? (size_t)n * max_boxes * DIPS_LINK_WORDS : 1u);
+        std::vector<uint32_t> shape_recs(sane && shapes ? (size_t)n * max_boxes * DIPS_SHAPE_WORDS : 1u);
         std::vector<uint32_t> ids(sane && tracks ? 1u + 2u * (size_t)max_boxes : 1u);  // the state: [0] counts the tracks
         std::vector<uint16_t> state(state_values(sane, bg, sd, p.format, rw, rh));
         const char* what = nullptr;
@@ -1072,10 +1098,16 @@ int run_series(int argc, char** argv) {
             what = "dips_mask_tracks";
             st = dips_mask_tracks(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, nullptr, ids.data(),
                                   counts.data(), recs.data(), links.data());
-        } else if (st == DIPS_OK) {
+        } else if (st == DIPS_OK && !shapes) {
             what = "dips_mask_components";
             st = dips_mask_components(hd, mask.data(), n, rw, rh, connectivity, min_area, max_boxes, 0u, counts.data(),
                                       max_boxes ? recs.data() : nullptr, nullptr);
+        }
+        if (st == DIPS_OK && shapes) {  // the same counts and records once more, and their shapes
+            what = "dips_mask_shapes";
+            st = dips_mask_shapes(hd, mask.data(), weights.p, n, rw, rh, connectivity, min_area, max_boxes, 0u,
+                                  counts.data(), max_boxes ? recs.data() : nullptr,
+                                  max_boxes ? shape_recs.data() : nullptr);
         }
         StatsOut stats_out;
         if (st == DIPS_OK) st = mask_stats(hd, mask, n, rw, rh, stats, &stats_out, &what);
@@ -1091,7 +1123,8 @@ int run_series(int argc, char** argv) {
             std::fprintf(stderr, "dips_raw: cannot write %s\n", out_path);
             return 1;
         }
-        std::fprintf(f, "frame,k,x0,y0,x1,y1,area,anchor,cx256,cy256%s\n", tracks ? ",prev,overlap,track,age" : "");
+        std::fprintf(f, "frame,k,x0,y0,x1,y1,area,anchor,cx256,cy256%s%s\n", tracks ? ",prev,overlap,track,age" : "",
+                     shapes ? ",sx,sy,sxx,syy,sxy,wsum,wmax,cracks_v,cracks_h,euler" : "");
         unsigned long long total = 0, stored = 0;
         for (uint32_t t = 0; t < n; ++t) {
             std::fprintf(f, "# %u,%u\n", t, counts[t]);
@@ -1104,6 +1137,13 @@ int run_series(int argc, char** argv) {
                     const uint32_t* l = &links[((size_t)t * max_boxes + k) * DIPS_LINK_WORDS];
                     std::fprintf(f, ",%u,%u,%u,%u", l[DIPS_LINK_PREV], l[DIPS_LINK_OVERLAP], l[DIPS_LINK_TRACK],
                                  l[DIPS_LINK_AGE]);
+                }
+                if (shapes) {
+                    const uint32_t* q = &shape_recs[((size_t)t * max_boxes + k) * DIPS_SHAPE_WORDS];
+                    for (uint32_t fld = DIPS_SHAPE_SX; fld <= DIPS_SHAPE_WSUM; fld += 2u)
+                        std::fprintf(f, ",%llu", (unsigned long long)q[fld] | ((unsigned long long)q[fld + 1u] << 32));
+                    std::fprintf(f, ",%u,%u,%u,%d", q[DIPS_SHAPE_WMAX], q[DIPS_SHAPE_CRACKS_V], q[DIPS_SHAPE_CRACKS_H],
+                                 (int32_t)q[DIPS_SHAPE_EULER]);
                 }
                 std::fprintf(f, "\n");
             }
@@ -1121,6 +1161,7 @@ int run_series(int argc, char** argv) {
         print_select(sel);
         print_background(bg, sd);
         print_mask_stats(stats);
+        if (shapes) std::printf(" shapes=1");
         std::printf("\n");
         return 0;
     }

@@ -1,9 +1,9 @@
 // mask_abi.hip -- host side of include/dips_hip.h, part 5: the products of a
-// packed change mask -- its connected components, the components linked
-// across frames (tracks), the binary morphology, the temporal vote, the
-// selection of components with the word-wise logic, and the statistics (grid
-// counts, change times and per-pixel sums).  What
-// they share with the series and the regional products is in series_host.h.
+// packed change mask -- its connected components and their shape records,
+// the components linked across frames (tracks), the binary morphology, the
+// temporal vote, the selection of components with the word-wise logic, and
+// the statistics (grid counts, change times and per-pixel sums).  What they
+// share with the series and the regional products is in series_host.h.
 // Every extern "C" body runs inside dips_abi::guard (abi_guard.h).
 #include <hip/hip_runtime.h>
 
@@ -19,8 +19,9 @@ using namespace dips_internal;
 namespace {
 
 // ---------------------------------------------------------------------------
-// The connected components of a mask (dips_mask_components; kernels in
-// mask_components.hip)
+// The connected components of a mask and their shape records
+// (dips_mask_components, dips_mask_shapes; kernels in mask_components.hip and
+// mask_shapes.hip)
 // ---------------------------------------------------------------------------
 
 constexpr size_t kComponentsScratchBytes = (size_t)1 << 30;  // chunk_frames = 0 stays within this
@@ -66,10 +67,13 @@ dips_status check_aligned4(dips_handle* h, const char* name, std::initializer_li
 }
 
 // Label the frames of a device mask, asynchronously on `s`, `chunk` frames
-// per round (0: automatic) in the handle's scratch.
+// per round (0: automatic) in the handle's scratch.  With `shapes`
+// (dips_mask_shapes; max_boxes > 0) every round also adds its shape records,
+// under `weights` if given (kernel in mask_shapes.hip).
 dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
                                   uint32_t connectivity, uint32_t min_area, uint32_t max_boxes, uint32_t chunk,
-                                  uint32_t* counts, uint32_t* boxes, uint32_t* labels, hipStream_t s) {
+                                  uint32_t* counts, uint32_t* boxes, uint32_t* labels, hipStream_t s,
+                                  const uint8_t* weights = nullptr, uint32_t* shapes = nullptr) {
     dips::ComponentsArgs a = components_args(w, hgt, connectivity, min_area);
     a.max_boxes = max_boxes;
     // per frame: parent, six statistics (two of 8 bytes) per slot, the block sums
@@ -95,6 +99,9 @@ dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t 
     // the records no component fills are zeros
     if (max_boxes != 0u)
         DIPS_HIP(h, hipMemsetAsync(boxes, 0, sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes, s));
+    // and the waves of shapes_kernel add onto the shape records
+    if (shapes)
+        DIPS_HIP(h, hipMemsetAsync(shapes, 0, sizeof(uint32_t) * DIPS_SHAPE_WORDS * (size_t)n_frames * max_boxes, s));
     const size_t frame_words = (size_t)a.wpf;
     for (uint32_t t = 0; t < n_frames; t += F) {
         a.n_frames = std::min(F, n_frames - t);
@@ -103,6 +110,13 @@ dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t 
         a.boxes = max_boxes != 0u ? boxes + (size_t)t * max_boxes * DIPS_BOX_WORDS : nullptr;
         a.labels = labels ? labels + (size_t)t * a.npx : nullptr;
         DIPS_HIP(h, dips::launch_mask_components(a, s));
+        if (shapes) {
+            dips::ShapesArgs g{};
+            g.cc = a;
+            g.weights = weights ? weights + (size_t)t * a.npx : nullptr;
+            g.shapes = shapes + (size_t)t * max_boxes * DIPS_SHAPE_WORDS;
+            DIPS_HIP(h, dips::launch_mask_shapes(g, s));
+        }
     }
     return span.end(s);
 }
@@ -591,6 +605,58 @@ dips_status dips_mask_components(dips_handle* h, const uint8_t* mask, uint32_t n
         if (max_boxes != 0u)
             DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
         if (labels) DIPS_HIP(h, hipMemcpyAsync(labels, h->stage_map.p, labels_bytes, hipMemcpyDeviceToHost, h->stream));
+        DIPS_HIP(h, hipStreamSynchronize(h->stream));
+        return DIPS_OK;
+    });
+}
+
+dips_status dips_mask_shapes(dips_handle* h, const uint8_t* mask, const uint8_t* weights, uint32_t n_frames,
+                             uint32_t roi_w, uint32_t roi_h, uint32_t connectivity, uint32_t min_area,
+                             uint32_t max_boxes, uint32_t chunk_frames, uint32_t* counts, uint32_t* boxes,
+                             uint32_t* shapes) {
+    return guard(h, [&]() -> dips_status {
+        dips_status st = bind(h);
+        if (st != DIPS_OK) return st;
+        if (n_frames == 0) return DIPS_OK;
+        if (!mask || !counts || ((!boxes || !shapes) && max_boxes != 0u))
+            return fail(h, DIPS_ERR_INVALID, "mask_shapes: null argument");
+        DIPS_TRY(check_labelling(h, "mask_shapes", n_frames, roi_w, roi_h, connectivity, max_boxes));
+        if (roi_w > 65536u || roi_h > 65536u)
+            return fail(h, DIPS_ERR_INVALID, "mask_shapes: roi_w and roi_h must be at most 65536");
+        if ((uint64_t)n_frames * max_boxes * DIPS_SHAPE_WORDS >= (1ull << 32))
+            return fail(h, DIPS_ERR_INVALID, "mask_shapes: n_frames * max_boxes * 16 must stay below 2^32");
+        if (max_boxes == 0u) boxes = shapes = nullptr;
+        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
+            DIPS_TRY(check_aligned4(h, "mask_shapes", {mask, counts, boxes}));
+            if (((uintptr_t)shapes & 7u) != 0)
+                return fail(h, DIPS_ERR_INVALID, "mask_shapes: shapes must be 8-byte aligned");
+            return run_components_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
+                                         chunk_frames, counts, boxes, nullptr, h->stream, weights, shapes);
+        }
+        // host pointers: stage through HBM (synchronous call); the weights
+        // behind the mask, the shapes (8-byte aligned) in front of boxes and counts
+        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const size_t weights_bytes = weights ? (size_t)roi_w * roi_h * n_frames : 0u;
+        const size_t counts_bytes = sizeof(uint32_t) * (size_t)n_frames;
+        const size_t boxes_bytes = sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
+        const size_t shapes_bytes = sizeof(uint32_t) * DIPS_SHAPE_WORDS * (size_t)n_frames * max_boxes;
+        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes + weights_bytes));
+        DIPS_HIP(h, h->stage_series.ensure(shapes_bytes + boxes_bytes + counts_bytes));
+        uint8_t* mask_dev = h->stage_frames.as<uint8_t>();
+        uint8_t* weights_dev = weights ? mask_dev + mask_bytes : nullptr;
+        uint32_t* shapes_dev = max_boxes != 0u ? h->stage_series.as<uint32_t>() : nullptr;
+        uint32_t* boxes_dev = max_boxes != 0u ? shapes_dev + shapes_bytes / sizeof(uint32_t) : nullptr;
+        uint32_t* counts_dev = h->stage_series.as<uint32_t>() + (shapes_bytes + boxes_bytes) / sizeof(uint32_t);
+        DIPS_HIP(h, hipMemcpyAsync(mask_dev, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
+        if (weights) DIPS_HIP(h, hipMemcpyAsync(weights_dev, weights, weights_bytes, hipMemcpyHostToDevice, h->stream));
+        st = run_components_device(h, mask_dev, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
+                                   chunk_frames, counts_dev, boxes_dev, nullptr, h->stream, weights_dev, shapes_dev);
+        if (st != DIPS_OK) return st;
+        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (max_boxes != 0u) {
+            DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
+            DIPS_HIP(h, hipMemcpyAsync(shapes, shapes_dev, shapes_bytes, hipMemcpyDeviceToHost, h->stream));
+        }
         DIPS_HIP(h, hipStreamSynchronize(h->stream));
         return DIPS_OK;
     });

@@ -1,7 +1,7 @@
 // mask_labelling.h -- what the kernels behind the labelling share with it
-// (mask_components.hip, mask_select.hip): the thread's word of a chunk, the
-// mask word with its pad bits cleared, the statistics slot of a node and the
-// relaxed load of a parent.
+// (mask_components.hip, mask_select.hip, mask_shapes.hip): the thread's word
+// of a chunk, the mask word with its pad bits cleared, the statistics slot of
+// a node and the relaxed load of a parent.
 #pragma once
 
 #include <hip/hip_runtime.h>

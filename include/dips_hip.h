@@ -605,6 +605,67 @@ dips_status dips_mask_tracks(dips_handle *h, const uint8_t *mask, uint32_t n_fra
                              const uint8_t *prev_mask, uint32_t *state,
                              uint32_t *counts, uint32_t *boxes, uint32_t *links);
 
+/* The shape of every component of a change mask: exact second-order moments
+ * (elongation, orientation), the crack perimeter (compactness), the Euler
+ * number (holes) and the sum and peak of a per-pixel weight (how strongly it
+ * changed): what a box cannot say.  The reference has no counterpart.  Every
+ * field is an integer sum over the set bits of a component, hence exact.
+ * mask, roi_w, roi_h, connectivity, min_area, max_boxes (K), chunk_frames,
+ * counts and boxes mean exactly what they mean in dips_mask_components, and
+ * counts and boxes of this call equal that call's, word for word, on the same
+ * arguments; so do dips_mask_tracks', so shapes record k of frame t describes
+ * the component of link record k.
+ * weights: NULL (no weights) or n_frames*roi_h*roi_w bytes, one u8 per pixel
+ * of the region, row stride roi_w, at any byte alignment.  Nothing produces
+ * it inside this call: the abs-diff map of a whole-frame GRAY8 series, or any
+ * saliency plane of the caller's.
+ * shapes[(t*K + k)*DIPS_SHAPE_WORDS + f] for k < min(counts[t], K); every
+ * other record is zeros and every word of shapes is written.  With C the set
+ * of pixels (i, j) of the component, region-relative; the 64-bit fields are
+ * stored as (low word, high word) at even word offsets:
+ *   SX, SY, SXX, SYY, SXY  the sums over C of i, j, i*i, j*j, i*j (64 bits);
+ *   WSUM   the sum over C of weight(i, j) (64 bits); 0 without weights;
+ *   WMAX   the largest weight(i, j) over C; 0 without weights;
+ *   CRACKS_V  the number of pairs (p in C, horizontal neighbour q = (i-1, j)
+ *          or (i+1, j)) with q clear or outside the region;
+ *   CRACKS_H  the same for the vertical neighbours (i, j-1) and (i, j+1);
+ *   EULER  int32 in two's complement: 1 minus the number of holes of C taken
+ *          alone.  The holes are the bounded connected components of the
+ *          complement of C in the plane under the dual connectivity (4 when
+ *          connectivity is 8, 8 when it is 4); everything outside the region
+ *          is background.  A component that lies inside a hole of C does not
+ *          fill it.
+ * A set horizontal or vertical neighbour of a pixel of C is in C under both
+ * connectivities, so the crack fields depend on the bits alone; CRACKS_V +
+ * CRACKS_H is the crack perimeter, CRACKS_V / 2 the number of maximal row
+ * runs of C.  The area is boxes' AREA.
+ * chunk_frames, the scratch, DIPS_FLAG_TIME_KERNEL (one entry for all
+ * launches of the call) and n_frames == 0 as in dips_mask_components; the
+ * result does not depend on chunk_frames.  DIPS_FLAG_DEVICE_PTRS: device
+ * pointers, the call asynchronous on the handle's stream; shapes must be
+ * 8-byte aligned, mask, counts and boxes 4-byte aligned, weights may have any
+ * alignment; else host pointers of any alignment, staged through HBM,
+ * synchronous.  DIPS_ERR_INVALID, outputs untouched: that call's cases, and
+ * roi_w or roi_h above 65536 (every sum stays below 2^62),
+ * n_frames*max_boxes*DIPS_SHAPE_WORDS >= 2^32, null shapes with max_boxes >
+ * 0, a misaligned shapes.  DIPS_ERR_NOMEM if the scratch cannot be allocated. */
+#define DIPS_SHAPE_SX 0u
+#define DIPS_SHAPE_SY 2u
+#define DIPS_SHAPE_SXX 4u
+#define DIPS_SHAPE_SYY 6u
+#define DIPS_SHAPE_SXY 8u
+#define DIPS_SHAPE_WSUM 10u
+#define DIPS_SHAPE_WMAX 12u
+#define DIPS_SHAPE_CRACKS_V 13u
+#define DIPS_SHAPE_CRACKS_H 14u
+#define DIPS_SHAPE_EULER 15u
+#define DIPS_SHAPE_WORDS 16u
+dips_status dips_mask_shapes(dips_handle *h, const uint8_t *mask, const uint8_t *weights,
+                             uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
+                             uint32_t connectivity, uint32_t min_area, uint32_t max_boxes,
+                             uint32_t chunk_frames,
+                             uint32_t *counts, uint32_t *boxes, uint32_t *shapes);
+
 /* The binary morphology of a change mask, frame by frame: the cleanup
  * between threshold and components (difference -> threshold -> morphology ->
  * components -> boxes).  The reference has no counterpart.  A second stage

@@ -221,6 +221,9 @@ extern "C" {
                             connectivity: u32, min_area: u32, max_boxes: u32, chunk_frames: u32,
                             prev_mask: *const u8, state: *mut u32, counts: *mut u32, boxes: *mut u32,
                             links: *mut u32) -> DipsStatus;
+    pub fn dips_mask_shapes(h: *mut DipsHandle, mask: *const u8, weights: *const u8, n_frames: u32, roi_w: u32,
+                            roi_h: u32, connectivity: u32, min_area: u32, max_boxes: u32, chunk_frames: u32,
+                            counts: *mut u32, boxes: *mut u32, shapes: *mut u32) -> DipsStatus;
     pub fn dips_mask_morph(h: *mut DipsHandle, mask_in: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, op: u32,
                            shape: u32, rx: u32, ry: u32, mask_out: *mut u8) -> DipsStatus;
     pub fn dips_mask_vote(h: *mut DipsHandle, mask_in: *const u8, n_frames: u32, roi_w: u32, roi_h: u32, window: u32,
