@@ -12,7 +12,11 @@ waves every series and regional launch runs and how its frames are cut.
   resident wave slots of the one or two kernel forms (from CUs x waves per
   SIMD under the DIPS_SERIES_WAVES_PER_SIMD cap), the DIPS_PIXEL_PART_FRAMES
   pin, and the kernels' constants (pixels per vec, vecs per lane, kPixMaxPart /
-  the summaries' byte budget / the table kernel's waves per group).
+  the summaries' byte budget / the table kernel's waves per group).  Two more
+  products, not in the table, serve tests/_round_cases.py: 8 the vote on a
+  mask rw x rh (unroll: words per lane, aux: the window), 9 the times and sums
+  of a mask (ppv: pixels per lane slot, aux: a part's summary bytes, pin: the
+  summaries' byte budget).
 * The schedules the project has recorded, at 4,096 wave slots.
 * tests/_sched.py part_schedule agrees with the header on the series rows."""
 import os
@@ -56,6 +60,14 @@ int main() {
             case 3: q = pix_geometry(fb, n, unroll, rw, rh, res_a, (uint32_t)aux, pin); break;
             case 4: q = mask_geometry(fb, n, unroll, rw, rh, res_a); break;
             case 5: q = times_geometry(fb, n, unroll, rw, rh, aux, pin, two); break;
+            case 8: q = vote_geometry(mask_words_per_row(rw) * rh, n, (uint32_t)aux, unroll, res_a); break;
+            case 9: {
+                // as run_mask_times_device asks: the several-parts form first, then the one-part form's slots
+                const uint64_t slots = 4u * mask_words_per_row(rw) * rh * (8u / (uint64_t)ppv);
+                q = mask_times_geometry(slots, n, aux, pin, res_a);
+                if (q.ok && q.parts == 1u) q = mask_times_geometry(slots, n, aux, 0u, res_b);
+                break;
+            }
             default: q = background_geometry(fb, n, unroll, rw, rh, [&](bool small) { return two(!small); }); break;
         }
         int tail_rows = 0;
