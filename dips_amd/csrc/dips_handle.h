@@ -11,7 +11,8 @@
 //                   statistics
 //   shard_abi.hip   the frame-range sharding of the series
 // (series_host.h: what the series, region and mask units share; series_sched.h:
-// their schedules as functions of plain numbers.)
+// their schedules as functions of plain numbers; mask_host.h and
+// mask_scratch.h: the mask unit's staging, checks and scratch plan.)
 //
 // The handle plays the role of the reference's ComputeState
 // (dips/src/gpu/mod.rs:39-56): it owns the HIP device binding, the stream,

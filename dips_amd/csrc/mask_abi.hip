@@ -4,14 +4,19 @@
 // temporal vote, the selection of components with the word-wise logic, and
 // the statistics (grid counts, change times and per-pixel sums).  What they
 // share with the series and the regional products is in series_host.h.
+// The labelling family (components, shapes, select, tracks) takes its rounds
+// and its scratch from one plan (mask_scratch.h label_scratch, applied by
+// plan_labelling); every entry point is argument checks, its pointers added
+// to a HostStaging (mask_host.h, with the checks they share), one call of a
+// run_*_device function and finish().
 // Every extern "C" body runs inside dips_abi::guard (abi_guard.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <initializer_list>
 #include <string>
 
-#include "series_host.h"
+#include "mask_host.h"
+#include "mask_scratch.h"
 
 using dips_abi::guard;
 using namespace dips_internal;
@@ -23,8 +28,6 @@ namespace {
 // (dips_mask_components, dips_mask_shapes; kernels in mask_components.hip and
 // mask_shapes.hip)
 // ---------------------------------------------------------------------------
-
-constexpr size_t kComponentsScratchBytes = (size_t)1 << 30;  // chunk_frames = 0 stays within this
 
 // The labelling's view of a w x hgt mask (components and tracks)
 dips::ComponentsArgs components_args(uint32_t w, uint32_t hgt, uint32_t connectivity, uint32_t min_area) {
@@ -57,12 +60,24 @@ dips_status check_labelling(dips_handle* h, const char* name, uint32_t n_frames,
     return DIPS_OK;
 }
 
-// the device pointers of a call, all 4-byte aligned
-dips_status check_aligned4(dips_handle* h, const char* name, std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* p : ptrs) bits |= (uintptr_t)p;
-    if ((bits & 3u) != 0)
-        return fail(h, DIPS_ERR_INVALID, std::string(name) + ": the device pointers must be 4-byte aligned");
+// The rounds of a labelling call over n_frames frames, `chunk` per round (0:
+// automatic), and its scratch (mask_scratch.h; K: 0, or the tracks'
+// max_boxes): the handle's cc_scratch grown to the plan -- before the timed
+// span, growing synchronises -- and a's planes pointed into it.
+dips_status plan_labelling(dips_handle* h, dips::ComponentsArgs& a, uint32_t n_frames, uint32_t chunk, uint32_t K,
+                           dips_sched::LabelScratch* plan) {
+    const dips_sched::LabelScratch p = dips_sched::label_scratch(a.npx, a.nslots, a.bpf, n_frames, chunk, K);
+    DIPS_HIP(h, h->cc_scratch.ensure((size_t)p.bytes));
+    uint8_t* b = h->cc_scratch.as<uint8_t>();
+    a.sum_i = reinterpret_cast<uint64_t*>(b + p.sum_i);
+    a.sum_j = reinterpret_cast<uint64_t*>(b + p.sum_j);
+    a.area = reinterpret_cast<uint32_t*>(b + p.area);
+    a.min_x = reinterpret_cast<uint32_t*>(b + p.min_x);
+    a.max_x = reinterpret_cast<uint32_t*>(b + p.max_x);
+    a.max_y = reinterpret_cast<uint32_t*>(b + p.max_y);
+    a.parent = reinterpret_cast<uint32_t*>(b + p.parent);
+    a.block_count = reinterpret_cast<uint32_t*>(b + p.block_count);
+    *plan = p;
     return DIPS_OK;
 }
 
@@ -76,23 +91,9 @@ dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t 
                                   const uint8_t* weights = nullptr, uint32_t* shapes = nullptr) {
     dips::ComponentsArgs a = components_args(w, hgt, connectivity, min_area);
     a.max_boxes = max_boxes;
-    // per frame: parent, six statistics (two of 8 bytes) per slot, the block sums
-    const size_t per_frame = 4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf;
-    uint64_t frames = chunk ? chunk : std::max<uint64_t>(1u, kComponentsScratchBytes / per_frame);
-    frames = std::min<uint64_t>(frames, n_frames);
-    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
-    const uint32_t F = (uint32_t)frames;
-    // the scratch before the timed span (growing it synchronises)
-    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F));
-    uint8_t* base = h->cc_scratch.as<uint8_t>();
-    a.sum_i = reinterpret_cast<uint64_t*>(base);
-    a.sum_j = a.sum_i + (size_t)F * a.nslots;
-    a.area = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);
-    a.min_x = a.area + (size_t)F * a.nslots;
-    a.max_x = a.min_x + (size_t)F * a.nslots;
-    a.max_y = a.max_x + (size_t)F * a.nslots;
-    a.parent = a.max_y + (size_t)F * a.nslots;
-    a.block_count = a.parent + (size_t)F * a.npx;
+    dips_sched::LabelScratch plan;
+    DIPS_TRY(plan_labelling(h, a, n_frames, chunk, 0u, &plan));
+    const uint32_t F = plan.F;
 
     KernelSpan span(h);
     DIPS_TRY(span.begin(s));
@@ -126,9 +127,20 @@ dips_status run_components_device(dips_handle* h, const uint8_t* mask, uint32_t 
 // mask_components.hip and mask_tracks.hip)
 // ---------------------------------------------------------------------------
 
-// tr_ids_kernel walks a chain back to the chunk's first frame at most: the
-// cap keeps that walk, one dependent load per frame, short whatever the clip
-constexpr uint32_t kTracksChunkFrames = 256;
+// the geometry the tracks' kernels share with the labelling's
+dips::TracksArgs tracks_args(const dips::ComponentsArgs& a, uint32_t K) {
+    dips::TracksArgs tr{};
+    tr.w = a.w;
+    tr.h = a.h;
+    tr.npx = a.npx;
+    tr.wpr = a.wpr;
+    tr.hw = a.hw;
+    tr.nslots = a.nslots;
+    tr.wpf = a.wpf;
+    tr.bpf = a.bpf;
+    tr.K = K;
+    return tr;
+}
 
 // Label and link the frames of a device mask, asynchronously on `s`, `chunk`
 // frames per round (0: automatic) in the handle's scratch.  The parent and
@@ -142,51 +154,23 @@ dips_status run_tracks_device(dips_handle* h, const uint8_t* mask, uint32_t n_fr
                               const uint8_t* prev_mask, uint32_t* state, uint32_t* counts, uint32_t* boxes,
                               uint32_t* links, hipStream_t s) {
     dips::ComponentsArgs a = components_args(w, hgt, connectivity, min_area);
-    // per frame: the labelling's share, the overlap table, cprev and hrank, heads and base;
-    // once: the plane in front of parent and of the labels, next id, a count, two carries
-    const size_t per_frame =
-        4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf + 4u * (size_t)K * K + 8u * (size_t)K + 8u;
-    const size_t fixed = 4u * (size_t)a.npx + 4u * (size_t)a.nslots + 16u * (size_t)K + 8u;
-    uint64_t frames =
-        chunk ? chunk
-              : std::max<uint64_t>(1u, (kComponentsScratchBytes - std::min(fixed, kComponentsScratchBytes)) / per_frame);
-    frames = std::min<uint64_t>(frames, n_frames);
-    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
-    frames = std::min<uint64_t>(frames, kTracksChunkFrames);
-    const uint32_t F = (uint32_t)frames;
-    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F + fixed));
-    uint8_t* base = h->cc_scratch.as<uint8_t>();
-    a.sum_i = reinterpret_cast<uint64_t*>(base);
-    a.sum_j = a.sum_i + (size_t)F * a.nslots;
-    uint32_t* label0 = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);  // F + 1 planes
-    a.area = label0 + a.nslots;
-    a.min_x = a.area + (size_t)F * a.nslots;
-    a.max_x = a.min_x + (size_t)F * a.nslots;
-    a.max_y = a.max_x + (size_t)F * a.nslots;
-    uint32_t* parent0 = a.max_y + (size_t)F * a.nslots;  // F + 1 planes
-    a.parent = parent0 + a.npx;
-    a.block_count = a.parent + (size_t)F * a.npx;
+    dips_sched::LabelScratch plan;
+    DIPS_TRY(plan_labelling(h, a, n_frames, chunk, K, &plan));
+    const uint32_t F = plan.F;
+    uint8_t* scratch = h->cc_scratch.as<uint8_t>();
+    const auto at = [scratch](uint64_t off) { return reinterpret_cast<uint32_t*>(scratch + off); };
 
-    dips::TracksArgs tr{};
-    tr.parent = parent0;
-    tr.label = label0;
-    tr.ov = a.block_count + (size_t)F * a.bpf;
-    tr.cprev = tr.ov + (size_t)F * K * K;
-    tr.hrank = tr.cprev + (size_t)F * K;
-    tr.heads = tr.hrank + (size_t)F * K;
-    tr.base = tr.heads + F;
-    tr.next_id = tr.base + F;
-    uint32_t* prev_count = tr.next_id + 1;
-    uint32_t* carry[2] = {prev_count + 1, prev_count + 1 + 2u * (size_t)K};
-    tr.w = a.w;
-    tr.h = a.h;
-    tr.npx = a.npx;
-    tr.wpr = a.wpr;
-    tr.hw = a.hw;
-    tr.nslots = a.nslots;
-    tr.wpf = a.wpf;
-    tr.bpf = a.bpf;
-    tr.K = K;
+    dips::TracksArgs tr = tracks_args(a, K);
+    tr.parent = at(plan.parent0);  // F + 1 planes
+    tr.label = at(plan.label0);    // F + 1 planes
+    tr.ov = at(plan.ov);
+    tr.cprev = at(plan.cprev);
+    tr.hrank = at(plan.hrank);
+    tr.heads = at(plan.heads);
+    tr.base = at(plan.base);
+    tr.next_id = at(plan.next_id);
+    uint32_t* prev_count = at(plan.prev_count);
+    uint32_t* carry[2] = {at(plan.carry[0]), at(plan.carry[1])};
 
     KernelSpan span(h);
     DIPS_TRY(span.begin(s));
@@ -313,15 +297,9 @@ dips_status run_vote_device(dips_handle* h, const uint8_t* mask_in, uint32_t n_f
 // mask_select.hip)
 // ---------------------------------------------------------------------------
 
-// whether two byte ranges share a byte
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && na != 0 && nb != 0 && pa < pb + nb && pb < pa + na;
-}
-
 // Label the frames of a device mask and write the components selected,
 // asynchronously on `s`, `chunk` frames per round (0: automatic) in the
-// handle's scratch, laid out as run_components_device lays it out.  marker
+// handle's scratch, planned as for run_components_device.  marker
 // NULL: none; else marker_frames (1 or n_frames) frames.  counts NULL: none.
 dips_status run_select_device(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t w, uint32_t hgt,
                               uint32_t connectivity, uint32_t min_area, uint32_t max_area, uint32_t select,
@@ -333,22 +311,9 @@ dips_status run_select_device(dips_handle* h, const uint8_t* mask, uint32_t n_fr
     g.max_area = max_area;
     g.select = select;
     g.marker_stride = marker && marker_frames != 1u ? a.wpf : 0u;
-    const size_t per_frame = 4u * (size_t)a.npx + 32u * (size_t)a.nslots + 4u * (size_t)a.bpf;
-    uint64_t frames = chunk ? chunk : std::max<uint64_t>(1u, kComponentsScratchBytes / per_frame);
-    frames = std::min<uint64_t>(frames, n_frames);
-    frames = std::min<uint64_t>(frames, std::max<uint64_t>(1u, (1u << 25) / a.bpf));  // the launches' block counts
-    const uint32_t F = (uint32_t)frames;
-    // the scratch before the timed span (growing it synchronises)
-    DIPS_HIP(h, h->cc_scratch.ensure(per_frame * F));
-    uint8_t* base = h->cc_scratch.as<uint8_t>();
-    a.sum_i = reinterpret_cast<uint64_t*>(base);
-    a.sum_j = a.sum_i + (size_t)F * a.nslots;
-    a.area = reinterpret_cast<uint32_t*>(a.sum_j + (size_t)F * a.nslots);
-    a.min_x = a.area + (size_t)F * a.nslots;
-    a.max_x = a.min_x + (size_t)F * a.nslots;
-    a.max_y = a.max_x + (size_t)F * a.nslots;
-    a.parent = a.max_y + (size_t)F * a.nslots;
-    a.block_count = a.parent + (size_t)F * a.npx;
+    dips_sched::LabelScratch plan;
+    DIPS_TRY(plan_labelling(h, a, n_frames, chunk, 0u, &plan));
+    const uint32_t F = plan.F;
 
     KernelSpan span(h);
     DIPS_TRY(span.begin(s));
@@ -486,11 +451,8 @@ extern "C" {
 dips_status dips_mask_counts(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
                              uint32_t rows, uint32_t cols, uint32_t* counts) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
-        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_counts: roi_w and roi_h must not be 0");
-        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
-            return fail(h, DIPS_ERR_INVALID, "mask_counts: the region must stay below 2^30 pixels");
+        DIPS_TRY(bind(h));
+        DIPS_TRY(check_mask_region(h, "mask_counts", roi_w, roi_h));
         if (rows == 0 || cols == 0) return fail(h, DIPS_ERR_INVALID, "mask_counts: rows and cols must be at least 1");
         if (rows > roi_h || cols > roi_w)
             return fail(h, DIPS_ERR_INVALID,
@@ -499,72 +461,47 @@ dips_status dips_mask_counts(dips_handle* h, const uint8_t* mask, uint32_t n_fra
             return fail(h, DIPS_ERR_INVALID, "mask_counts: n_frames * rows * cols must stay below 2^30");
         if (n_frames == 0) return DIPS_OK;
         if (!mask || !counts) return fail(h, DIPS_ERR_INVALID, "mask_counts: null argument");
-        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const size_t mask_bytes = mask_frame_bytes(roi_w, roi_h) * n_frames;
         const size_t counts_bytes = sizeof(uint32_t) * (size_t)n_frames * rows * cols;
-        if (ranges_overlap(counts, counts_bytes, mask, mask_bytes))
+        if (outputs_overlap({{counts, counts_bytes}}, {{mask, mask_bytes}}))
             return fail(h, DIPS_ERR_INVALID, "mask_counts: counts must not overlap mask");
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_counts", {mask, counts}));
-            return run_counts_device(h, mask, n_frames, roi_w, roi_h, rows, cols, counts, h->stream);
-        }
-        // host pointers: stage through HBM (synchronous call)
-        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes));
-        DIPS_HIP(h, h->stage_series.ensure(counts_bytes));
-        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
-        st = run_counts_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, rows, cols,
-                               h->stage_series.as<uint32_t>(), h->stream);
-        if (st != DIPS_OK) return st;
-        DIPS_HIP(h, hipMemcpyAsync(counts, h->stage_series.p, counts_bytes, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        HostStaging sg(h, "mask_counts");
+        sg.add(h->stage_frames, mask, mask_bytes, sg.kIn);
+        sg.add(h->stage_series, counts, counts_bytes, sg.kOut);
+        DIPS_TRY(sg.begin());
+        DIPS_TRY(run_counts_device(h, mask, n_frames, roi_w, roi_h, rows, cols, counts, h->stream));
+        return sg.finish();
     });
 }
 
 dips_status dips_mask_pixel_times(dips_handle* h, const uint8_t* mask, uint32_t n_frames, uint32_t roi_w,
                                   uint32_t roi_h, uint32_t t0, uint32_t accumulate, uint32_t* times, uint32_t* sums) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (!times && !sums) return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: times and sums are both null");
         if (!mask && n_frames > 0) return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: null argument");
-        if (roi_w == 0 || roi_h == 0)
-            return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: roi_w and roi_h must not be 0");
-        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
-            return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: the region must stay below 2^30 pixels");
+        DIPS_TRY(check_mask_region(h, "mask_pixel_times", roi_w, roi_h));
         if (times && (uint64_t)t0 + n_frames > 0xFFFFFFFFull)
             return fail(h, DIPS_ERR_INVALID,
                         "mask_pixel_times: t0 + n_frames must stay below 2^32 (index 0xFFFFFFFF is DIPS_TIME_NONE)");
         const size_t npx = (size_t)roi_w * roi_h;
-        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
+        const size_t mask_bytes = mask_frame_bytes(roi_w, roi_h) * n_frames;
         const size_t times_bytes = times ? sizeof(uint32_t) * DIPS_TIMES_PLANES * npx : 0u;
         const size_t sums_bytes = sums ? sizeof(uint32_t) * npx : 0u;
-        if (ranges_overlap(times, times_bytes, mask, mask_bytes) || ranges_overlap(sums, sums_bytes, mask, mask_bytes) ||
-            ranges_overlap(times, times_bytes, sums, sums_bytes))
+        if (outputs_overlap({{times, times_bytes}, {sums, sums_bytes}}, {{mask, mask_bytes}}))
             return fail(h, DIPS_ERR_INVALID, "mask_pixel_times: an output must not overlap the mask or the other output");
         if (n_frames == 0) mask = nullptr;
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_pixel_times", {mask, times, sums}));
-            return run_mask_times_device(h, mask, n_frames, roi_w, roi_h, t0, accumulate != 0u, times, sums, h->stream);
-        }
-        if (n_frames == 0 && accumulate != 0u) return DIPS_OK;
-        // host pointers: stage through HBM (synchronous call); the sums behind
-        // the times, the state uploaded first when accumulating
-        if (mask_bytes) DIPS_HIP(h, h->stage_frames.ensure(mask_bytes));
-        DIPS_HIP(h, h->stage_series.ensure(times_bytes + sums_bytes));
-        uint32_t* times_dev = times ? h->stage_series.as<uint32_t>() : nullptr;
-        uint32_t* sums_dev = sums ? h->stage_series.as<uint32_t>() + times_bytes / sizeof(uint32_t) : nullptr;
-        if (mask_bytes) DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
-        if (accumulate != 0u) {
-            if (times) DIPS_HIP(h, hipMemcpyAsync(times_dev, times, times_bytes, hipMemcpyHostToDevice, h->stream));
-            if (sums) DIPS_HIP(h, hipMemcpyAsync(sums_dev, sums, sums_bytes, hipMemcpyHostToDevice, h->stream));
-        }
-        st = run_mask_times_device(h, mask_bytes ? h->stage_frames.as<uint8_t>() : nullptr, n_frames, roi_w, roi_h, t0,
-                                   accumulate != 0u, times_dev, sums_dev, h->stream);
-        if (st != DIPS_OK) return st;
-        if (times) DIPS_HIP(h, hipMemcpyAsync(times, times_dev, times_bytes, hipMemcpyDeviceToHost, h->stream));
-        if (sums) DIPS_HIP(h, hipMemcpyAsync(sums, sums_dev, sums_bytes, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        // the sums behind the times, the state uploaded first when accumulating
+        HostStaging sg(h, "mask_pixel_times");
+        const unsigned state = accumulate != 0u ? sg.kInOut : sg.kOut;
+        sg.add(h->stage_frames, mask, mask_bytes, sg.kIn);
+        sg.add(h->stage_series, times, times_bytes, state);
+        sg.add(h->stage_series, sums, sums_bytes, state);
+        DIPS_TRY(sg.check_aligned4());
+        if (n_frames == 0 && accumulate != 0u) return DIPS_OK;  // nothing to add: nothing is staged
+        DIPS_TRY(sg.upload());
+        DIPS_TRY(run_mask_times_device(h, mask, n_frames, roi_w, roi_h, t0, accumulate != 0u, times, sums, h->stream));
+        return sg.finish();
     });
 }
 
@@ -572,41 +509,23 @@ dips_status dips_mask_components(dips_handle* h, const uint8_t* mask, uint32_t n
                                  uint32_t roi_h, uint32_t connectivity, uint32_t min_area, uint32_t max_boxes,
                                  uint32_t chunk_frames, uint32_t* counts, uint32_t* boxes, uint32_t* labels) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (n_frames == 0) return DIPS_OK;
         if (!mask || !counts || (!boxes && max_boxes != 0u))
             return fail(h, DIPS_ERR_INVALID, "mask_components: null argument");
         DIPS_TRY(check_labelling(h, "mask_components", n_frames, roi_w, roi_h, connectivity, max_boxes));
-        const uint64_t n_px = (uint64_t)roi_w * roi_h;
         if (max_boxes == 0u) boxes = nullptr;
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_components", {mask, counts, boxes, labels}));
-            return run_components_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
-                                         chunk_frames, counts, boxes, labels, h->stream);
-        }
-        // host pointers: stage through HBM (synchronous call); counts and
-        // boxes share one buffer
-        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
         const size_t counts_bytes = sizeof(uint32_t) * (size_t)n_frames;
-        const size_t boxes_bytes = sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
-        const size_t labels_bytes = labels ? sizeof(uint32_t) * (size_t)n_px * n_frames : 0u;
-        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes));
-        DIPS_HIP(h, h->stage_series.ensure(counts_bytes + boxes_bytes));
-        if (labels) DIPS_HIP(h, h->stage_map.ensure(labels_bytes));
-        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
-        uint32_t* counts_dev = h->stage_series.as<uint32_t>();
-        uint32_t* boxes_dev = max_boxes != 0u ? counts_dev + n_frames : nullptr;
-        st = run_components_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, connectivity, min_area,
-                                   max_boxes, chunk_frames, counts_dev, boxes_dev,
-                                   labels ? h->stage_map.as<uint32_t>() : nullptr, h->stream);
-        if (st != DIPS_OK) return st;
-        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, h->stream));
-        if (max_boxes != 0u)
-            DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
-        if (labels) DIPS_HIP(h, hipMemcpyAsync(labels, h->stage_map.p, labels_bytes, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        // counts and boxes share one buffer
+        HostStaging sg(h, "mask_components");
+        sg.add(h->stage_frames, mask, mask_frame_bytes(roi_w, roi_h) * n_frames, sg.kIn);
+        sg.add(h->stage_series, counts, counts_bytes, sg.kOut);
+        sg.add(h->stage_series, boxes, counts_bytes * DIPS_BOX_WORDS * max_boxes, sg.kOut);
+        sg.add(h->stage_map, labels, counts_bytes * roi_w * roi_h, sg.kOut);
+        DIPS_TRY(sg.begin());
+        DIPS_TRY(run_components_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
+                                       chunk_frames, counts, boxes, labels, h->stream));
+        return sg.finish();
     });
 }
 
@@ -615,8 +534,7 @@ dips_status dips_mask_shapes(dips_handle* h, const uint8_t* mask, const uint8_t*
                              uint32_t max_boxes, uint32_t chunk_frames, uint32_t* counts, uint32_t* boxes,
                              uint32_t* shapes) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (n_frames == 0) return DIPS_OK;
         if (!mask || !counts || ((!boxes || !shapes) && max_boxes != 0u))
             return fail(h, DIPS_ERR_INVALID, "mask_shapes: null argument");
@@ -626,39 +544,22 @@ dips_status dips_mask_shapes(dips_handle* h, const uint8_t* mask, const uint8_t*
         if ((uint64_t)n_frames * max_boxes * DIPS_SHAPE_WORDS >= (1ull << 32))
             return fail(h, DIPS_ERR_INVALID, "mask_shapes: n_frames * max_boxes * 16 must stay below 2^32");
         if (max_boxes == 0u) boxes = shapes = nullptr;
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_shapes", {mask, counts, boxes}));
-            if (((uintptr_t)shapes & 7u) != 0)
-                return fail(h, DIPS_ERR_INVALID, "mask_shapes: shapes must be 8-byte aligned");
-            return run_components_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
-                                         chunk_frames, counts, boxes, nullptr, h->stream, weights, shapes);
-        }
-        // host pointers: stage through HBM (synchronous call); the weights
-        // behind the mask, the shapes (8-byte aligned) in front of boxes and counts
-        const size_t mask_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
-        const size_t weights_bytes = weights ? (size_t)roi_w * roi_h * n_frames : 0u;
         const size_t counts_bytes = sizeof(uint32_t) * (size_t)n_frames;
-        const size_t boxes_bytes = sizeof(uint32_t) * DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
-        const size_t shapes_bytes = sizeof(uint32_t) * DIPS_SHAPE_WORDS * (size_t)n_frames * max_boxes;
-        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes + weights_bytes));
-        DIPS_HIP(h, h->stage_series.ensure(shapes_bytes + boxes_bytes + counts_bytes));
-        uint8_t* mask_dev = h->stage_frames.as<uint8_t>();
-        uint8_t* weights_dev = weights ? mask_dev + mask_bytes : nullptr;
-        uint32_t* shapes_dev = max_boxes != 0u ? h->stage_series.as<uint32_t>() : nullptr;
-        uint32_t* boxes_dev = max_boxes != 0u ? shapes_dev + shapes_bytes / sizeof(uint32_t) : nullptr;
-        uint32_t* counts_dev = h->stage_series.as<uint32_t>() + (shapes_bytes + boxes_bytes) / sizeof(uint32_t);
-        DIPS_HIP(h, hipMemcpyAsync(mask_dev, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
-        if (weights) DIPS_HIP(h, hipMemcpyAsync(weights_dev, weights, weights_bytes, hipMemcpyHostToDevice, h->stream));
-        st = run_components_device(h, mask_dev, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
-                                   chunk_frames, counts_dev, boxes_dev, nullptr, h->stream, weights_dev, shapes_dev);
-        if (st != DIPS_OK) return st;
-        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, h->stream));
-        if (max_boxes != 0u) {
-            DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, boxes_bytes, hipMemcpyDeviceToHost, h->stream));
-            DIPS_HIP(h, hipMemcpyAsync(shapes, shapes_dev, shapes_bytes, hipMemcpyDeviceToHost, h->stream));
-        }
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        // the weights (bytes) behind the mask, the shapes (8-byte aligned) in
+        // front of boxes and counts
+        HostStaging sg(h, "mask_shapes");
+        sg.add(h->stage_frames, mask, mask_frame_bytes(roi_w, roi_h) * n_frames, sg.kIn);
+        sg.add(h->stage_frames, weights, (size_t)roi_w * roi_h * n_frames, sg.kIn | sg.kAnyAlign);
+        sg.add(h->stage_series, shapes, counts_bytes * DIPS_SHAPE_WORDS * max_boxes, sg.kOut | sg.kAnyAlign);
+        sg.add(h->stage_series, boxes, counts_bytes * DIPS_BOX_WORDS * max_boxes, sg.kOut);
+        sg.add(h->stage_series, counts, counts_bytes, sg.kOut);
+        DIPS_TRY(sg.check_aligned4());
+        if (sg.device() && ((uintptr_t)shapes & 7u) != 0)
+            return fail(h, DIPS_ERR_INVALID, "mask_shapes: shapes must be 8-byte aligned");
+        DIPS_TRY(sg.upload());
+        DIPS_TRY(run_components_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes,
+                                       chunk_frames, counts, boxes, nullptr, h->stream, weights, shapes));
+        return sg.finish();
     });
 }
 
@@ -667,49 +568,26 @@ dips_status dips_mask_tracks(dips_handle* h, const uint8_t* mask, uint32_t n_fra
                              const uint8_t* prev_mask, uint32_t* state, uint32_t* counts, uint32_t* boxes,
                              uint32_t* links) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (n_frames == 0) return DIPS_OK;
         if (!mask || !counts || !boxes || !links) return fail(h, DIPS_ERR_INVALID, "mask_tracks: null argument");
         if (max_boxes == 0u || max_boxes > DIPS_TRACK_MAX_BOXES)
             return fail(h, DIPS_ERR_INVALID, "mask_tracks: max_boxes must be 1 .. 256");
         if (prev_mask && !state) return fail(h, DIPS_ERR_INVALID, "mask_tracks: prev_mask needs state");
         DIPS_TRY(check_labelling(h, "mask_tracks", n_frames, roi_w, roi_h, connectivity, max_boxes));
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_tracks", {mask, prev_mask, state, counts, boxes, links}));
-            return run_tracks_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes, chunk_frames,
-                                     prev_mask, state, counts, boxes, links, h->stream);
-        }
-        // host pointers: stage through HBM (synchronous call); the frame
-        // before the clip behind the mask, the outputs and the state in one buffer
-        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
-        const size_t mask_bytes = frame_bytes * n_frames;
-        const size_t counts_words = (size_t)n_frames;
-        const size_t boxes_words = DIPS_BOX_WORDS * (size_t)n_frames * max_boxes;
-        const size_t links_words = DIPS_LINK_WORDS * (size_t)n_frames * max_boxes;
-        const size_t state_words = 1u + 2u * (size_t)max_boxes;
-        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes + frame_bytes));
-        DIPS_HIP(h, h->stage_series.ensure(sizeof(uint32_t) * (counts_words + boxes_words + links_words + state_words)));
-        uint8_t* mask_dev = h->stage_frames.as<uint8_t>();
-        uint8_t* prev_dev = prev_mask ? mask_dev + mask_bytes : nullptr;
-        uint32_t* counts_dev = h->stage_series.as<uint32_t>();
-        uint32_t* boxes_dev = counts_dev + counts_words;
-        uint32_t* links_dev = boxes_dev + boxes_words;
-        uint32_t* state_dev = state ? links_dev + links_words : nullptr;
-        DIPS_HIP(h, hipMemcpyAsync(mask_dev, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
-        if (prev_mask) DIPS_HIP(h, hipMemcpyAsync(prev_dev, prev_mask, frame_bytes, hipMemcpyHostToDevice, h->stream));
-        if (state)
-            DIPS_HIP(h, hipMemcpyAsync(state_dev, state, sizeof(uint32_t) * state_words, hipMemcpyHostToDevice, h->stream));
-        st = run_tracks_device(h, mask_dev, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes, chunk_frames,
-                               prev_dev, state_dev, counts_dev, boxes_dev, links_dev, h->stream);
-        if (st != DIPS_OK) return st;
-        DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, sizeof(uint32_t) * counts_words, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipMemcpyAsync(boxes, boxes_dev, sizeof(uint32_t) * boxes_words, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipMemcpyAsync(links, links_dev, sizeof(uint32_t) * links_words, hipMemcpyDeviceToHost, h->stream));
-        if (state)
-            DIPS_HIP(h, hipMemcpyAsync(state, state_dev, sizeof(uint32_t) * state_words, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        const size_t frame_bytes = mask_frame_bytes(roi_w, roi_h), counts_bytes = sizeof(uint32_t) * (size_t)n_frames;
+        // the frame before the clip behind the mask, the outputs and the state in one buffer
+        HostStaging sg(h, "mask_tracks");
+        sg.add(h->stage_frames, mask, frame_bytes * n_frames, sg.kIn);
+        sg.add(h->stage_frames, prev_mask, frame_bytes, sg.kIn);
+        sg.add(h->stage_series, counts, counts_bytes, sg.kOut);
+        sg.add(h->stage_series, boxes, counts_bytes * DIPS_BOX_WORDS * max_boxes, sg.kOut);
+        sg.add(h->stage_series, links, counts_bytes * DIPS_LINK_WORDS * max_boxes, sg.kOut);
+        sg.add(h->stage_series, state, sizeof(uint32_t) * (1u + 2u * (size_t)max_boxes), sg.kInOut);
+        DIPS_TRY(sg.begin());
+        DIPS_TRY(run_tracks_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_boxes, chunk_frames,
+                                   prev_mask, state, counts, boxes, links, h->stream));
+        return sg.finish();
     });
 }
 
@@ -717,8 +595,7 @@ dips_status dips_mask_morph(dips_handle* h, const uint8_t* mask_in, uint32_t n_f
                             uint32_t roi_h, uint32_t op, uint32_t shape, uint32_t rx, uint32_t ry,
                             uint8_t* mask_out) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (n_frames == 0) return DIPS_OK;
         if (!mask_in || !mask_out) return fail(h, DIPS_ERR_INVALID, "mask_morph: null argument");
         if (op > DIPS_MORPH_CLOSE) return fail(h, DIPS_ERR_INVALID, "mask_morph: op must be 0 .. 3");
@@ -727,28 +604,16 @@ dips_status dips_mask_morph(dips_handle* h, const uint8_t* mask_in, uint32_t n_f
             return fail(h, DIPS_ERR_INVALID, "mask_morph: rx and ry must be 0 .. 15");
         if (shape == DIPS_MORPH_DIAMOND && ry != rx)
             return fail(h, DIPS_ERR_INVALID, "mask_morph: a diamond needs ry == rx");
-        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_morph: roi_w and roi_h must not be 0");
-        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
-            return fail(h, DIPS_ERR_INVALID, "mask_morph: the region must stay below 2^30 pixels");
-        const size_t bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h) * n_frames;
-        const uintptr_t pi = (uintptr_t)mask_in, po = (uintptr_t)mask_out;
-        if (pi < po + bytes && po < pi + bytes)
+        DIPS_TRY(check_mask_region(h, "mask_morph", roi_w, roi_h));
+        const size_t bytes = mask_frame_bytes(roi_w, roi_h) * n_frames;
+        if (outputs_overlap({{mask_out, bytes}}, {{mask_in, bytes}}))
             return fail(h, DIPS_ERR_INVALID, "mask_morph: mask_in and mask_out must not overlap");
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            if (((pi | po) & 3u) != 0)
-                return fail(h, DIPS_ERR_INVALID, "mask_morph: the device pointers must be 4-byte aligned");
-            return run_morph_device(h, mask_in, n_frames, roi_w, roi_h, op, shape, rx, ry, mask_out, h->stream);
-        }
-        // host pointers: stage through HBM (synchronous call)
-        DIPS_HIP(h, h->stage_frames.ensure(bytes));
-        DIPS_HIP(h, h->stage_map.ensure(bytes));
-        DIPS_HIP(h, hipMemcpyAsync(h->stage_frames.p, mask_in, bytes, hipMemcpyHostToDevice, h->stream));
-        st = run_morph_device(h, h->stage_frames.as<uint8_t>(), n_frames, roi_w, roi_h, op, shape, rx, ry,
-                              h->stage_map.as<uint8_t>(), h->stream);
-        if (st != DIPS_OK) return st;
-        DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        HostStaging sg(h, "mask_morph");
+        sg.add(h->stage_frames, mask_in, bytes, sg.kIn);
+        sg.add(h->stage_map, mask_out, bytes, sg.kOut);
+        DIPS_TRY(sg.begin());
+        DIPS_TRY(run_morph_device(h, mask_in, n_frames, roi_w, roi_h, op, shape, rx, ry, mask_out, h->stream));
+        return sg.finish();
     });
 }
 
@@ -756,52 +621,30 @@ dips_status dips_mask_vote(dips_handle* h, const uint8_t* mask_in, uint32_t n_fr
                            uint32_t window, uint32_t votes, const uint8_t* history_in, uint8_t* history_out,
                            uint8_t* mask_out) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (window == 0u || window > DIPS_VOTE_MAX_WINDOW) return fail(h, DIPS_ERR_INVALID, "mask_vote: window must be 1 .. 31");
         if (votes == 0u || votes > window) return fail(h, DIPS_ERR_INVALID, "mask_vote: votes must be 1 .. window");
-        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_vote: roi_w and roi_h must not be 0");
-        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
-            return fail(h, DIPS_ERR_INVALID, "mask_vote: the region must stay below 2^30 pixels");
+        DIPS_TRY(check_mask_region(h, "mask_vote", roi_w, roi_h));
         if (n_frames >= (1u << 31)) return fail(h, DIPS_ERR_INVALID, "mask_vote: n_frames must stay below 2^31");
         if (n_frames != 0 && (!mask_in || !mask_out)) return fail(h, DIPS_ERR_INVALID, "mask_vote: null argument");
         if (window == 1u) history_in = history_out = nullptr;  // there is no history
-        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        const size_t frame_bytes = mask_frame_bytes(roi_w, roi_h);
         const size_t bytes = frame_bytes * n_frames, hist_bytes = frame_bytes * (window - 1u);
-        // no output may share a byte with an input or with the other output
-        const auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-            const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-            return a && b && na != 0 && nb != 0 && pa < pb + nb && pb < pa + na;
-        };
-        if (overlap(mask_out, bytes, mask_in, bytes) || overlap(mask_out, bytes, history_in, hist_bytes) ||
-            overlap(history_out, hist_bytes, mask_in, bytes) || overlap(history_out, hist_bytes, history_in, hist_bytes) ||
-            overlap(mask_out, bytes, history_out, hist_bytes))
+        if (outputs_overlap({{mask_out, bytes}, {history_out, hist_bytes}}, {{mask_in, bytes}, {history_in, hist_bytes}}))
             return fail(h, DIPS_ERR_INVALID, "mask_vote: an output must not overlap an input or the other output");
         if (n_frames == 0) mask_in = mask_out = nullptr;
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_vote", {mask_in, mask_out, history_in, history_out}));
-            return run_vote_device(h, mask_in, n_frames, roi_w, roi_h, window, votes, history_in, history_out, mask_out,
-                                   h->stream);
-        }
-        if (n_frames == 0 && !history_out) return DIPS_OK;
-        // host pointers: stage through HBM (synchronous call); the history
-        // behind the mask, in and out alike
-        DIPS_HIP(h, h->stage_frames.ensure(bytes + hist_bytes));
-        DIPS_HIP(h, h->stage_map.ensure(bytes + hist_bytes));
-        uint8_t* in_dev = h->stage_frames.as<uint8_t>();
-        uint8_t* out_dev = h->stage_map.as<uint8_t>();
-        if (bytes) DIPS_HIP(h, hipMemcpyAsync(in_dev, mask_in, bytes, hipMemcpyHostToDevice, h->stream));
-        if (history_in)
-            DIPS_HIP(h, hipMemcpyAsync(in_dev + bytes, history_in, hist_bytes, hipMemcpyHostToDevice, h->stream));
-        st = run_vote_device(h, bytes ? in_dev : nullptr, n_frames, roi_w, roi_h, window, votes,
-                             history_in ? in_dev + bytes : nullptr, history_out ? out_dev + bytes : nullptr,
-                             bytes ? out_dev : nullptr, h->stream);
-        if (st != DIPS_OK) return st;
-        if (bytes) DIPS_HIP(h, hipMemcpyAsync(mask_out, out_dev, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (history_out)
-            DIPS_HIP(h, hipMemcpyAsync(history_out, out_dev + bytes, hist_bytes, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        // the history behind the mask, in and out alike
+        HostStaging sg(h, "mask_vote");
+        sg.add(h->stage_frames, mask_in, bytes, sg.kIn);
+        sg.add(h->stage_frames, history_in, hist_bytes, sg.kIn);
+        sg.add(h->stage_map, mask_out, bytes, sg.kOut);
+        sg.add(h->stage_map, history_out, hist_bytes, sg.kOut);
+        DIPS_TRY(sg.check_aligned4());
+        if (n_frames == 0 && !history_out) return DIPS_OK;  // nothing to write: nothing is staged
+        DIPS_TRY(sg.upload());
+        DIPS_TRY(run_vote_device(h, mask_in, n_frames, roi_w, roi_h, window, votes, history_in, history_out, mask_out,
+                                 h->stream));
+        return sg.finish();
     });
 }
 
@@ -810,8 +653,7 @@ dips_status dips_mask_select(dips_handle* h, const uint8_t* mask, uint32_t n_fra
                              const uint8_t* marker, uint32_t marker_frames, uint32_t chunk_frames, uint8_t* mask_out,
                              uint32_t* counts) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (n_frames == 0) return DIPS_OK;
         if (!mask || !mask_out) return fail(h, DIPS_ERR_INVALID, "mask_select: null argument");
         DIPS_TRY(check_labelling(h, "mask_select", n_frames, roi_w, roi_h, connectivity, 0u));
@@ -822,46 +664,28 @@ dips_status dips_mask_select(dips_handle* h, const uint8_t* mask, uint32_t n_fra
         if (marker ? (marker_frames != 1u && marker_frames != n_frames) : marker_frames != 0u)
             return fail(h, DIPS_ERR_INVALID,
                         "mask_select: marker_frames must be 1 or n_frames with a marker and 0 without");
-        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        const size_t frame_bytes = mask_frame_bytes(roi_w, roi_h);
         const size_t mask_bytes = frame_bytes * n_frames, marker_bytes = frame_bytes * marker_frames;
         const size_t counts_bytes = counts ? sizeof(uint32_t) * (size_t)n_frames : 0u;
-        if (ranges_overlap(mask_out, mask_bytes, mask, mask_bytes) ||
-            ranges_overlap(mask_out, mask_bytes, marker, marker_bytes) ||
-            ranges_overlap(counts, counts_bytes, mask, mask_bytes) ||
-            ranges_overlap(counts, counts_bytes, marker, marker_bytes) ||
-            ranges_overlap(counts, counts_bytes, mask_out, mask_bytes))
+        if (outputs_overlap({{mask_out, mask_bytes}, {counts, counts_bytes}}, {{mask, mask_bytes}, {marker, marker_bytes}}))
             return fail(h, DIPS_ERR_INVALID, "mask_select: an output must not overlap an input or the other output");
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_select", {mask, marker, mask_out, counts}));
-            return run_select_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_area, select, marker,
-                                     marker_frames, chunk_frames, mask_out, counts, h->stream);
-        }
-        // host pointers: stage through HBM (synchronous call); the marker
-        // behind the mask
-        DIPS_HIP(h, h->stage_frames.ensure(mask_bytes + marker_bytes));
-        DIPS_HIP(h, h->stage_map.ensure(mask_bytes));
-        if (counts) DIPS_HIP(h, h->stage_series.ensure(counts_bytes));
-        uint8_t* mask_dev = h->stage_frames.as<uint8_t>();
-        uint8_t* marker_dev = marker ? mask_dev + mask_bytes : nullptr;
-        uint32_t* counts_dev = counts ? h->stage_series.as<uint32_t>() : nullptr;
-        DIPS_HIP(h, hipMemcpyAsync(mask_dev, mask, mask_bytes, hipMemcpyHostToDevice, h->stream));
-        if (marker) DIPS_HIP(h, hipMemcpyAsync(marker_dev, marker, marker_bytes, hipMemcpyHostToDevice, h->stream));
-        st = run_select_device(h, mask_dev, n_frames, roi_w, roi_h, connectivity, min_area, max_area, select,
-                               marker_dev, marker_frames, chunk_frames, h->stage_map.as<uint8_t>(), counts_dev,
-                               h->stream);
-        if (st != DIPS_OK) return st;
-        DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, mask_bytes, hipMemcpyDeviceToHost, h->stream));
-        if (counts) DIPS_HIP(h, hipMemcpyAsync(counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        // the marker behind the mask
+        HostStaging sg(h, "mask_select");
+        sg.add(h->stage_frames, mask, mask_bytes, sg.kIn);
+        sg.add(h->stage_frames, marker, marker_bytes, sg.kIn);
+        sg.add(h->stage_map, mask_out, mask_bytes, sg.kOut);
+        sg.add(h->stage_series, counts, counts_bytes, sg.kOut);
+        DIPS_TRY(sg.begin());
+        DIPS_TRY(run_select_device(h, mask, n_frames, roi_w, roi_h, connectivity, min_area, max_area, select, marker,
+                                   marker_frames, chunk_frames, mask_out, counts, h->stream));
+        return sg.finish();
     });
 }
 
 dips_status dips_mask_logic(dips_handle* h, const uint8_t* a, uint32_t n_frames, uint32_t roi_w, uint32_t roi_h,
                             uint32_t op, const uint8_t* b, uint32_t b_frames, uint8_t* mask_out) {
     return guard(h, [&]() -> dips_status {
-        dips_status st = bind(h);
-        if (st != DIPS_OK) return st;
+        DIPS_TRY(bind(h));
         if (n_frames == 0) return DIPS_OK;
         if (!a || !mask_out) return fail(h, DIPS_ERR_INVALID, "mask_logic: null argument");
         if (op > DIPS_LOGIC_NOT) return fail(h, DIPS_ERR_INVALID, "mask_logic: op must be 0 .. 4");
@@ -869,30 +693,19 @@ dips_status dips_mask_logic(dips_handle* h, const uint8_t* a, uint32_t n_frames,
             return fail(h, DIPS_ERR_INVALID, "mask_logic: NOT takes no b, every other op needs one");
         if (b && b_frames != 1u && b_frames != n_frames)
             return fail(h, DIPS_ERR_INVALID, "mask_logic: b_frames must be 1 or n_frames");
-        if (roi_w == 0 || roi_h == 0) return fail(h, DIPS_ERR_INVALID, "mask_logic: roi_w and roi_h must not be 0");
-        if ((uint64_t)roi_w * roi_h >= (1ull << 30))
-            return fail(h, DIPS_ERR_INVALID, "mask_logic: the region must stay below 2^30 pixels");
-        const size_t frame_bytes = (size_t)(4u * mask_words_per_row(roi_w) * roi_h);
+        DIPS_TRY(check_mask_region(h, "mask_logic", roi_w, roi_h));
+        const size_t frame_bytes = mask_frame_bytes(roi_w, roi_h);
         const size_t bytes = frame_bytes * n_frames, b_bytes = frame_bytes * b_frames;
-        if (ranges_overlap(mask_out, bytes, a, bytes) || ranges_overlap(mask_out, bytes, b, b_bytes))
+        if (outputs_overlap({{mask_out, bytes}}, {{a, bytes}, {b, b_bytes}}))
             return fail(h, DIPS_ERR_INVALID, "mask_logic: mask_out must not overlap an input");
-        if (h->p.flags & DIPS_FLAG_DEVICE_PTRS) {
-            DIPS_TRY(check_aligned4(h, "mask_logic", {a, b, mask_out}));
-            return run_logic_device(h, a, n_frames, roi_w, roi_h, op, b, b_frames, mask_out, h->stream);
-        }
-        // host pointers: stage through HBM (synchronous call); b behind a
-        DIPS_HIP(h, h->stage_frames.ensure(bytes + b_bytes));
-        DIPS_HIP(h, h->stage_map.ensure(bytes));
-        uint8_t* a_dev = h->stage_frames.as<uint8_t>();
-        uint8_t* b_dev = b ? a_dev + bytes : nullptr;
-        DIPS_HIP(h, hipMemcpyAsync(a_dev, a, bytes, hipMemcpyHostToDevice, h->stream));
-        if (b) DIPS_HIP(h, hipMemcpyAsync(b_dev, b, b_bytes, hipMemcpyHostToDevice, h->stream));
-        st = run_logic_device(h, a_dev, n_frames, roi_w, roi_h, op, b_dev, b_frames, h->stage_map.as<uint8_t>(),
-                              h->stream);
-        if (st != DIPS_OK) return st;
-        DIPS_HIP(h, hipMemcpyAsync(mask_out, h->stage_map.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        DIPS_HIP(h, hipStreamSynchronize(h->stream));
-        return DIPS_OK;
+        // b behind a
+        HostStaging sg(h, "mask_logic");
+        sg.add(h->stage_frames, a, bytes, sg.kIn);
+        sg.add(h->stage_frames, b, b_bytes, sg.kIn);
+        sg.add(h->stage_map, mask_out, bytes, sg.kOut);
+        DIPS_TRY(sg.begin());
+        DIPS_TRY(run_logic_device(h, a, n_frames, roi_w, roi_h, op, b, b_frames, mask_out, h->stream));
+        return sg.finish();
     });
 }
 

@@ -207,6 +207,21 @@ def test_clip_carry_on_the_device(op):
         same(got, ref, cut)
 
 
+def test_clip_carry_with_host_pointers(op):
+    """The same through host pointers, where prev_mask travels behind the
+    mask and the state, read and written, behind the outputs: 37 x 5, six
+    frames, four boxes, rounds of two frames, cut in the middle of a round."""
+    h, w, K = 5, 37, 4
+    mask = cref.pack(random_bits(6, h, w, 0.3, 5))
+    ref = want(mask, w, 8, 1, K)
+    assert ref[0].max() > K and (ref[2][1:, :, tref.PREV] != N).any()  # records beyond K, and links to carry
+    one = run_host(op, mask, w, 8, 1, K, chunk_frames=2, state=np.zeros(1 + 2 * K, dtype=np.uint32))
+    same(one, ref)
+    a = run_host(op, mask[:3], w, 8, 1, K, chunk_frames=2, state=np.zeros(1 + 2 * K, dtype=np.uint32))
+    b = run_host(op, mask[3:], w, 8, 1, K, chunk_frames=2, prev=mask[2], state=a[3])
+    same([np.concatenate([x, y]) for x, y in zip(a[:3], b[:3])] + [b[3]], ref)
+
+
 def test_state_without_prev_is_a_scene_cut(op):
     n, h, w, nobj, K, min_area, connectivity = tref.SETTINGS[2]
     mask = cref.pack(tref.moving_rectangles(6, n, h, w, nobj))
