@@ -4,18 +4,22 @@ shapes are the smallest at which each mechanism of mask_select.hip can go
 wrong: word and row edges, every side of the border, pad bits, a marker far
 from the anchor of a spiral and of a comb, runs longer than cc_rows_kernel
 walks back, frames and chunks, one 4K frame under the one-address hot spot,
+the logic beyond its grid's 2^15 blocks (the second trip of the stride loop),
 the pointer kinds, the refused arguments and a randomized draw."""
 import functools
+import os
 
 import numpy as np
 import pytest
 
 import _components_ref as cref
+import _reuse_cases as rc
 import _select_ref as sref
 
 pytestmark = pytest.mark.gpu
 
 WIDTHS = [1, 2, 31, 32, 33, 63, 64, 65, 97]
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dips_amd", "csrc")
 SENTINEL = 0xA5
 
 
@@ -335,6 +339,63 @@ def test_logic_on_more_frames_than_a_grid_dimension(op):
     assert np.array_equal(run_logic(op, a, sref.XOR, b, pad=1), cref.pack(a ^ b))
     assert np.array_equal(run_logic(op, a, sref.NOT, None, pad=1), cref.pack(~a))
     assert np.array_equal(run_logic(op, a, sref.ANDNOT, a[::-1]), cref.pack(a & ~a[::-1]))
+
+
+# -- beyond 2^15 blocks: the second trip of the grid stride ----------------------------------
+
+def _random_words(seed, n, h, wpr):
+    """uint32 [n, h, wpr]: a packed mask with random bits, the pad bits too."""
+    return np.random.default_rng([73, seed, n, h, wpr]).integers(0, 1 << 32, (n, h, wpr), dtype=np.uint32)
+
+
+def _logic_words(x, lop, y, pad_mask):
+    """The reference on the packed words themselves: (a op b) & pad_mask."""
+    v = {sref.AND: lambda: x & y, sref.OR: lambda: x | y, sref.XOR: lambda: x ^ y, sref.ANDNOT: lambda: x & ~y,
+         sref.NOT: lambda: ~x}[lop]()
+    return v & pad_mask
+
+
+def _check_logic_beyond_the_grid(op, case, runs):
+    """mask_logic_kernel's grid ends at kMaxBlocks blocks; beyond, a thread
+    strides on and carries r, its word's index in the frame, forward by dr
+    with a wrap.  r picks b's word under the broadcast and the words that get
+    the pad mask.  runs: (op, frames of b: 0 none, 1 broadcast, n)."""
+    import torch
+    from dips_amd import MaskLogic
+    name, w, h, n = case
+    g = rc.logic_geometry(w, h, n, rc.logic_max_blocks(CSRC))
+    assert g["words"] > g["stride"] and g["words"] % g["stride"] != 0 and g["dr"] != 0, g  # a second, ragged trip
+    wpr = (w + 31) // 32
+    a, b = _random_words(1, n, h, wpr), _random_words(2, n, h, wpr)
+    pad_mask = np.full(wpr, 0xFFFFFFFF, dtype=np.uint32)
+    if w % 32:
+        pad_mask[-1] = (1 << (w % 32)) - 1
+    dev = torch.device("cuda", op._dev.device)
+    da, db = (torch.from_numpy(x.view(np.uint8).reshape(n, h, 4 * wpr)).to(dev) for x in (a, b))
+    out = torch.empty_like(da)
+    for lop, b_frames in runs:
+        out.fill_(SENTINEL)
+        op.run_mask_logic_device(da, w, out, MaskLogic(lop), None if b_frames == 0 else db[:b_frames])
+        got = out.cpu().numpy().view(np.uint32).reshape(n, h, wpr)
+        want = _logic_words(a, lop, None if b_frames == 0 else b[:b_frames], pad_mask)
+        assert np.array_equal(got, want), (name, lop, b_frames, np.argwhere(got != want)[:5].tolist())
+        if w % 32:
+            assert not (got[..., -1] & ~pad_mask[-1]).any()  # the output's pad bits are 0
+
+
+def test_logic_beyond_the_grid_many_frames(op):
+    """300 frames of 1000 x 1000: 9.6 M words in frames of 32,000, dr = 4,608,
+    so r wraps on every trip at another place and the last trip is ragged."""
+    case = rc.LOGIC_CASES[0]
+    n = case[3]
+    runs = [(lop, k) for lop in (sref.AND, sref.OR, sref.XOR, sref.ANDNOT) for k in (n, 1)] + [(sref.NOT, 0)]
+    _check_logic_beyond_the_grid(op, case, runs)
+
+
+def test_logic_beyond_the_grid_one_frame_longer_than_the_grid(op):
+    """2 frames of 16,416 x 16,400: a frame of 8,413,200 words is longer than
+    the grid's 2^15 * 256 threads, so dr is the stride itself."""
+    _check_logic_beyond_the_grid(op, rc.LOGIC_CASES[1], [(sref.XOR, 1), (sref.NOT, 0)])
 
 
 # -- the composites -------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """dips_mask_counts and dips_mask_pixel_times on the GPU against
 tests/_mask_stats_ref.py, every output value.  The shapes are the smallest at
 which each mechanism of mask_stats.hip can go wrong: word and pad edges, cells
-that share, straddle and span words, column chunks and row bands, the seams of
+that share, straddle and span words, column chunks and row bands, more items
+than blocks (a block's second trip through its item loop), the seams of
 the frame parts (series_sched.h mask_times_geometry, read from the header
 itself), a clip fed in chunks, t0 at its limit, the refused arguments, parity
 with the fused products on the raw change mask, the one-call pipeline and a 4K
@@ -15,6 +16,7 @@ import pytest
 import _components_ref as cref
 import _mask_stats_ref as sref
 import _morph_ref as mref
+import _reuse_cases as rc
 import _vote_ref as vref
 
 pytestmark = pytest.mark.gpu
@@ -118,6 +120,28 @@ def test_the_banded_and_chunked_grids_are_what_they_claim(sched):
         q = sref.counts_geometry(sched, [(2500, 2, 1, 2500, 3, CHUNK_CELLS, MIN_BAND_WORDS, res),
                                          (4100, 300, 2, 3, 3, CHUNK_CELLS, MIN_BAND_WORDS, res)])
         assert q[0]["col_chunks"] >= 2 and q[1]["bands"] >= 2
+
+
+# -- more items than blocks: the second trip of a block's item loop ------------------------
+
+@pytest.mark.parametrize("case", rc.COUNTS_CASES, ids=lambda c: c[0])
+def test_counts_with_more_items_than_blocks(op, sched, case):
+    """mask_counts_kernel launches min(items, 2 * resident blocks) blocks and
+    a block loops it += gridDim.x, clearing its LDS cells at the top of every
+    trip.  A CU holds at most 2,048 threads, eight blocks of 256, so 8 * CUs
+    bounds the resident blocks: each case has more items than twice that
+    (test_mask_reuse_cpu.py shows it for 256, 2,048 and 8,192 without a GPU)."""
+    import torch
+    _, w, h, rows, cols, n, _ = case
+    resident = 8 * torch.cuda.get_device_properties(op._dev.device).multi_processor_count
+    q = sref.counts_geometry(sched, rc.counts_rows([case], CHUNK_CELLS, MIN_BAND_WORDS, resident))[0]
+    rc.check_counts_geometry(case, q, resident)
+    for density in (0.5, 1.0, 0.01):
+        bits = random_bits.__wrapped__(n, h, w, density, seed=rows)  # up to 41 MB: not kept
+        got = op.mask_counts(mask_of(bits), rows, cols)
+        same(got, sref.counts_bits(bits, rows, cols), (case[0], density))
+        assert np.array_equal(got.sum(axis=(1, 2), dtype=np.uint64), bits.sum(axis=(1, 2)))
+        assert got.any()
 
 
 def test_counts_device_path_writes_every_entry_and_nothing_else(op):
