@@ -21,6 +21,7 @@
 #include "abi_guard.h"
 #include "comm.h"
 #include "alt_lut.h"
+#include "batch_chunks.h"
 #include "dips_kernels.h"
 #include "host_buffers.h"
 #include "host_stream.h"
@@ -351,12 +352,10 @@ dips_status run_fast(dips_alt_handle* h, const uint8_t* frames, uint32_t n, cons
     const uint64_t U = lut ? (uint64_t)dips::kUnrollAltLut : (uint64_t)dips::kUnrollAlt;
     const uint64_t n_tiles = (n_vec + 64u * U - 1) / (64u * U);
     const uint64_t resident = (uint64_t)occ * 4u * (uint64_t)h->cu_count;
-    // chunks of >= 16 frames; enough (tile, chunk) items to fill the chip
-    uint64_t n_chunks = (resident + n_tiles - 1) / n_tiles;
-    n_chunks = std::min<uint64_t>(n_chunks, (n + 15u) / 16u);
-    n_chunks = std::max<uint64_t>(n_chunks, 1);
-    const uint32_t chunk = (uint32_t)((n + n_chunks - 1) / n_chunks);
-    n_chunks = (n + chunk - 1) / chunk;
+    // enough (tile, chunk) items to fill the chip, at most ceil(n / 16) chunks
+    const dips_sched::BatchChunks plan = dips_sched::batch_chunk_plan(n, n_tiles, resident);
+    const uint32_t chunk = plan.chunk;
+    const uint64_t n_chunks = plan.n_chunks;
     if (n_tiles * n_chunks >= (1ull << 31)) return fail(h, DIPS_ERR_INVALID, "batch too large; split it");
 
     // per-frame flags and per-chunk "last snapshot before the chunk", staged

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <utility>
 
+#include "batch_chunks.h"
 #include "dips_handle.h"
 #include "dips_kernels.h"
 
@@ -340,11 +341,10 @@ dips_status batch_steady(dips_handle* h, const uint8_t* bf, uint8_t* bo, uint32_
     const uint64_t n_vec = npx / 4u;
     const uint64_t U = lut ? (uint64_t)dips::kUnrollCompatLut : (uint64_t)dips::kUnrollCompatBatch;
     const uint64_t n_tiles = (n_vec + 64u * U - 1) / (64u * U);
-    uint64_t n_chunks = (resident + n_tiles - 1) / n_tiles;
-    n_chunks = std::min<uint64_t>(n_chunks, (m + 15u) / 16u);
-    n_chunks = std::max<uint64_t>(n_chunks, 1);
-    const uint32_t chunk = (uint32_t)((m + n_chunks - 1) / n_chunks);
-    n_chunks = (m + chunk - 1) / chunk;
+    // enough (tile, chunk) items to fill the chip, at most ceil(m / 16) chunks
+    const dips_sched::BatchChunks plan = dips_sched::batch_chunk_plan(m, n_tiles, resident);
+    const uint32_t chunk = plan.chunk;
+    const uint64_t n_chunks = plan.n_chunks;
     if (n_tiles * n_chunks >= (1ull << 31)) return fail(h, DIPS_ERR_INVALID, "batch too large; split it");
 
     dips::CompatBatchArgs a{};
