@@ -16,11 +16,10 @@ the one GPU of the box, ranks as loopback threads:
 * argument and state errors return on the rank that has them.
 
 The reference is single-device; the sharding is SURVEY.md s8e's."""
-import threading
-
 import numpy as np
 import pytest
 
+from _shard_loopback import alt_sharded as _sharded
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -47,52 +46,6 @@ def _one_loop(frames, props, markers, n_tex):
         return r(frames)
     finally:
         r.close()
-
-
-def _sharded(world, frames, props, markers, n_tex, device_ptrs, keep_last=False, crosscheck=False):
-    """dips_alt_run_sharded on `world` loopback ranks, one thread each;
-    returns the concatenated outputs (and the last rank's runner if asked)."""
-    import torch
-    from dips_amd.alt import DiPsRunner
-    from dips_amd.comm import Comm, shard_range
-    n, h, w = frames.shape[:3]
-    comms = Comm.loopback(world, 0)
-    runners = [DiPsRunner(h, w, props, markers, num_textures=n_tex, crosscheck=crosscheck) for _ in range(world)]
-    outs, errs = [None] * world, [None] * world
-
-    def rank(r):
-        try:
-            s, e = shard_range(n, world, r)
-            if device_ptrs:
-                dev = torch.from_numpy(frames[s:e].copy()).cuda()
-                out = torch.empty_like(dev)
-                runners[r].run_sharded_device(comms[r], dev, out, n)
-                outs[r] = out.cpu().numpy()
-            else:
-                outs[r] = runners[r].run_sharded(comms[r], frames[s:e], n)
-        except Exception as ex:  # reported below, on the test's thread
-            errs[r] = ex
-
-    if device_ptrs:
-        torch.cuda.synchronize()
-    th = [threading.Thread(target=rank, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(120)
-    try:
-        assert not any(t.is_alive() for t in th), "a rank did not return"
-        assert errs == [None] * world, errs
-        got = np.concatenate(outs) if n else np.empty((0, h, w, 4), dtype=np.uint8)
-        if keep_last:
-            last = runners.pop()
-            return got, last
-        return got
-    finally:
-        for r in runners:
-            r.close()
-        for c in comms:
-            c.close()
 
 
 CASES = [

@@ -23,6 +23,7 @@ import threading
 import numpy as np
 import pytest
 
+from _shard_loopback import compat_loopback as _compat_loopback
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -329,48 +330,6 @@ def test_sharded_argument_errors():
 
 
 # -- the dips-compat ComputeState over frame ranges ----------
-def _compat_loopback(world, n_total, w, h, props, device_ptrs):
-    import torch
-    from dips_amd import ComputeState
-    from dips_amd.comm import Comm, shard_range
-    frames = np.random.default_rng(world * 100 + n_total).integers(0, 256, (n_total, h, w, 4), dtype=np.uint8)
-    comms = Comm.loopback(world, 0)
-    states = [ComputeState(*props) for _ in range(world)]
-    outs, errors = [None] * world, []
-    try:
-        ranges = [shard_range(n_total, world, r) for r in range(world)]
-        if device_ptrs:
-            dev_in = [torch.from_numpy(frames[s:e].copy()).cuda() for s, e in ranges]
-            dev_out = [torch.empty_like(t) for t in dev_in]
-            torch.cuda.synchronize()
-
-        def rank(r):
-            try:
-                s, e = ranges[r]
-                if device_ptrs:
-                    states[r].frame_callback_batch_sharded_device(comms[r], dev_in[r], dev_out[r], n_total)
-                else:
-                    outs[r] = states[r].frame_callback_batch_sharded(comms[r], w, h, frames[s:e], n_total)
-            except Exception as ex:  # reported below
-                errors.append((r, repr(ex)))
-
-        threads = [threading.Thread(target=rank, args=(r,)) for r in range(world)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join(timeout=180)
-        assert not any(t.is_alive() for t in threads) and not errors, errors
-        if device_ptrs:
-            torch.cuda.synchronize()
-            outs = [o.cpu().numpy() for o in dev_out]
-        return frames, np.concatenate(outs)
-    finally:
-        for c in states:
-            c.close()
-        for c in comms:
-            c.close()
-
-
 @pytest.mark.parametrize("world,n_total", [(2, 19), (3, 31)])
 @pytest.mark.parametrize("window", [1, 3])
 @pytest.mark.parametrize("device_ptrs", [False, True])
